@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s of the MI355X-native Qwen3 forward path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--model qwen3-0.6b] [--batch 64]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full] [--model qwen3-0.6b] [--batch 64]
+
+A plain run does what the headline figure needs and no more: build the model, prefill once (untimed), W warm-up steps,
+K timed steps, the result line.  `--dump-outputs DIR` also writes what the last timed step returned to its caller
+(DIR/next_ids.npy).  Everything else the benchmark measures (per-kernel roofline, live PMC traffic, warmed prefill, CPU
+baseline, tensor-parallel leg and its projection) runs only with `--full` and is described below.
 
 One "step" = one decode step of the whole batch through the HIP path (libnvllm_amd.so, C ABI):
 every live sequence gets one new token; the greedy ids of every step come back to the host (the reference's
@@ -13,12 +18,12 @@ N = 1  Qwen3-0.6B shapes, 64 live sequences (BASELINE.json configs[2] steady sta
 N > 1  sequences are independent units: every GPU serves its own 64 sequences with the TP=1 path, no
        data-path collective => `value` = N x per-replica rate, "weak" scaling (--parallel tp serves ONE batch
        tensor-parallel instead).
-Every run also carries `tp_scaling`: decode tokens/s of Qwen3-32B (configs[4]: batch 64, prompt 128) at TP = N
+Every `--full` run also carries `tp_scaling`: decode tokens/s of Qwen3-32B (configs[4]: batch 64, prompt 128) at TP = N
 over RCCL (row/column-parallel linears, 2 all-reduces per layer, vocab-parallel LM head), so the N = 1, 2, 4, 8
 lines together are the TP=1/2/4/8 scaling curve the north_star asks for.
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel, HIP events on the
-library stream) and `cpu_baseline` (the C oracle in the reference's no-KV-cache mode on host cores).
+Prints ONE JSON line on rank 0 (driver contract); with `--full` it also holds `roofline` (dominant kernel, HIP events
+on the library stream) and `cpu_baseline` (the C oracle in the reference's no-KV-cache mode on host cores).
 """
 import argparse
 import json
@@ -37,6 +42,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "next_ids, the greedy token id of every live sequence; same arguments => same inputs => comparable between builds")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: warmed prefill timing, per-kernel HIP-event pass and roofline, "
+                         "live PMC traffic pass, CPU baseline, tensor-parallel leg and its projection (each still has its own switch)")
     ap.add_argument("--model", default="qwen3-0.6b", choices=["qwen3-0.6b", "qwen3-8b", "qwen3-32b", "tiny"])
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--prompt-min", type=int, default=64)
@@ -73,7 +84,10 @@ def parse():
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="plain `python bench.py --gpus N`: overall limit of the rank processes")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only (no GPU): every rank joins the gloo group, rank 0 prints the max rank seen")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def model_config(pkg, name):
@@ -292,7 +306,7 @@ def live_traffic(a, dom_kernel):
     cmd = ["rocprofv3", "--pmc", "FETCH_SIZE", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "r", "--",
            sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup),
            "--model", a.model, "--batch", str(a.batch), "--prompt-min", str(a.prompt_min), "--prompt-max", str(a.prompt_max),
-           "--seed", str(a.seed), "--profile-steps", str(a.profile_steps), "--no-cpu-baseline", "--skip-tp-leg", "--no-live-traffic",
+           "--seed", str(a.seed), "--profile-steps", str(a.profile_steps), "--full", "--no-cpu-baseline", "--skip-tp-leg", "--no-live-traffic",
            "--profile-meta"] + [x for o in a.option for x in ("--option", o)]
     try:
         cp = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=240)
@@ -401,35 +415,37 @@ def main():
     torch.cuda.synchronize()
     prefill_cold_s = time.perf_counter() - tp0
     prefill_tokens = sum(len(p) for p in prompts)
-    # warmed figure: the same prefill again (is_prefill restarts the sequences and re-uses their blocks); the first call
-    # also pays one-time costs (kernel code upload, LDS-size attributes, first touch of the step buffers)
-    reps = a.prefill_reps if a.prefill_only else 1
-    tw = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        tp0 = time.perf_counter()
-        model.step(seq_ids, prompts, is_prefill=True)
-        torch.cuda.synchronize()
-        tw.append(time.perf_counter() - tp0)
-    prefill_s = min(tw)
-    # prefill is the MFMA-bound side.  Algorithmic flops of what the kernels compute: the four layer projections on every
-    # prompt token, the LM head on the LAST row of every sequence only (compute_logits is needed for row len-1,
-    # llm_engine.rs:181-183; the reference runs it on all rows, qwen3.rs:548), attention reported as its own term.  The
-    # kernels issue 2x the projection flops on the MFMA pipe because activations are bf16 hi + lo.
-    layer_params = cfg.hidden_size * (cfg.num_attention_heads + 2 * cfg.num_key_value_heads) * cfg.head_dim \
-        + cfg.hidden_size * cfg.num_attention_heads * cfg.head_dim + 3 * cfg.hidden_size * cfg.intermediate_size
-    proj_flops = 2.0 * cfg.num_hidden_layers * layer_params * prefill_tokens
-    lm_flops = 2.0 * cfg.vocab_size * cfg.hidden_size * len(prompts)
-    attn_flops = 4.0 * cfg.num_attention_heads * cfg.head_dim * cfg.num_hidden_layers * sum(len(p) * (len(p) + 1) / 2 for p in prompts)
-    pf_tflops = (proj_flops + lm_flops) / prefill_s / 1e12
-    prefill_info = {"tokens": prefill_tokens, "ms": prefill_s * 1e3, "ms_first_call": prefill_cold_s * 1e3,
-                    "tokens_per_s": prefill_tokens / prefill_s, "algorithmic_tflops": pf_tflops,
-                    "algorithmic_flops": {"layer_projections": proj_flops, "lm_head_last_rows": lm_flops,
-                                          "attention_causal_not_in_frac": attn_flops},
-                    "mfma_peak_tflops_bf16_dense": 2500.0 * tpw, "frac_of_mfma_peak": pf_tflops / (2500.0 * tpw),
-                    "frac_of_mfma_peak_with_attention": (proj_flops + lm_flops + attn_flops) / prefill_s / 1e12 / (2500.0 * tpw),
-                    "note": "warmed (repeat of the same prefill); ms_first_call includes one-time setup; frac = (projections on "
-                            "all tokens + LM head on last rows) / time / dense bf16 peak"}
+    prefill_info = None
+    if a.full or a.prefill_only:
+        # warmed figure: the same prefill again (is_prefill restarts the sequences and re-uses their blocks); the first call
+        # also pays one-time costs (kernel code upload, LDS-size attributes, first touch of the step buffers)
+        reps = a.prefill_reps if a.prefill_only else 1
+        tw = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            tp0 = time.perf_counter()
+            model.step(seq_ids, prompts, is_prefill=True)
+            torch.cuda.synchronize()
+            tw.append(time.perf_counter() - tp0)
+        prefill_s = min(tw)
+        # prefill is the MFMA-bound side.  Algorithmic flops of what the kernels compute: the four layer projections on every
+        # prompt token, the LM head on the LAST row of every sequence only (compute_logits is needed for row len-1,
+        # llm_engine.rs:181-183; the reference runs it on all rows, qwen3.rs:548), attention reported as its own term.  The
+        # kernels issue 2x the projection flops on the MFMA pipe because activations are bf16 hi + lo.
+        layer_params = cfg.hidden_size * (cfg.num_attention_heads + 2 * cfg.num_key_value_heads) * cfg.head_dim \
+            + cfg.hidden_size * cfg.num_attention_heads * cfg.head_dim + 3 * cfg.hidden_size * cfg.intermediate_size
+        proj_flops = 2.0 * cfg.num_hidden_layers * layer_params * prefill_tokens
+        lm_flops = 2.0 * cfg.vocab_size * cfg.hidden_size * len(prompts)
+        attn_flops = 4.0 * cfg.num_attention_heads * cfg.head_dim * cfg.num_hidden_layers * sum(len(p) * (len(p) + 1) / 2 for p in prompts)
+        pf_tflops = (proj_flops + lm_flops) / prefill_s / 1e12
+        prefill_info = {"tokens": prefill_tokens, "ms": prefill_s * 1e3, "ms_first_call": prefill_cold_s * 1e3,
+                        "tokens_per_s": prefill_tokens / prefill_s, "algorithmic_tflops": pf_tflops,
+                        "algorithmic_flops": {"layer_projections": proj_flops, "lm_head_last_rows": lm_flops,
+                                              "attention_causal_not_in_frac": attn_flops},
+                        "mfma_peak_tflops_bf16_dense": 2500.0 * tpw, "frac_of_mfma_peak": pf_tflops / (2500.0 * tpw),
+                        "frac_of_mfma_peak_with_attention": (proj_flops + lm_flops + attn_flops) / prefill_s / 1e12 / (2500.0 * tpw),
+                        "note": "warmed (repeat of the same prefill); ms_first_call includes one-time setup; frac = (projections on "
+                                "all tokens + LM head on last rows) / time / dense bf16 peak"}
     if a.prefill_only:
         if rank == 0:
             print(json.dumps({"metric": "prefill tokens/sec", "value": prefill_tokens / prefill_s, "unit": "tokens/s",
@@ -463,7 +479,7 @@ def main():
         model.decode_enqueue()
         bytes_total += model.last_step_bytes
         model.decode_collect()
-    model.decode_collect()
+    last_ids = model.decode_collect()  # what the caller receives from the last timed step
     all_step_tokens += [int(ctx_lens.sum()) + i * a.batch for i in range(a.steps)]
     ctx_lens += a.steps
     torch.cuda.synchronize()
@@ -478,6 +494,35 @@ def main():
     replicas = 1 if use_tp else world
     tok_s = replicas * a.batch * a.steps / dt  # whole job: every replica serves its own batch
     mean_ctx = float(ctx_lens.mean()) - a.steps / 2
+
+    step_gbs = (bytes_total / a.steps) / (ev_ms / a.steps * 1e-3) / 1e9
+    opts = dict(o.partition("=")[::2] for o in a.option)
+    kv_desc = {("16", "16"): "f16", ("16", "24"): "f16 K / 24-bit V (f16 + bf8 residual)", ("24", "24"): "24-bit K and V (f16 + bf8 residual)"}.get(
+        (opts.get("kv_k_bits", "16"), opts.get("kv_v_bits", "16")), "f16")
+    out = {
+        "metric": "decode tokens/sec", "value": tok_s, "unit": "tokens/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong" if use_tp else "weak", "vs_baseline": None,
+        "dtype": f"bf16 weights, {kv_desc} KV cache, bf16x2(hi+lo)/f16 MFMA operands, f32 accumulate",
+        "data": "synthetic",
+        "config": {"workload": f"{a.model} decode, {a.batch} live sequences, prompts U[{a.prompt_min},{a.prompt_max}] seed {a.seed}",
+                   **({"options": list(a.option)} if a.option else {}),
+                   "batch": a.batch, "global_batch": a.batch * replicas, "mean_context": round(mean_ctx, 1),
+                   "parallelism": f"tp{world}" if use_tp else (f"dp{world} x tp1 (independent replicas, no collective)" if world > 1 else "tp1")},
+        "step_roofline": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": step_gbs / HBM_PEAK_GBS, "bytes_per_step": bytes_total / a.steps,
+                          "event_ms_per_step": ev_ms / a.steps},
+    }
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "next_ids.npy"), last_ids[:a.batch].astype(np.float64))
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # per-kernel HIP-event pass (outside the timed region; same process, same resident state)
     kern = {}
@@ -526,7 +571,6 @@ def main():
     else:
         dom_bytes = None
         dom_name = dom
-    step_gbs = (bytes_total / a.steps) / (ev_ms / a.steps * 1e-3) / 1e9
     raw_us = dom_ms / max(dom_n, 1) * 1e3
     launch_us = max(raw_us - bracket_us, 1e-3)  # bracketed duration minus the calibrated empty bracket
     roof = {"bound": "hbm", "kernel": dom_name, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
@@ -553,25 +597,8 @@ def main():
         roof["achieved"] = dom_bytes / (launch_us * 1e-6) / 1e9
         roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
         roof["bytes_per_launch"] = dom_bytes
-    opts = dict(o.partition("=")[::2] for o in a.option)
-    kv_desc = {("16", "16"): "f16", ("16", "24"): "f16 K / 24-bit V (f16 + bf8 residual)", ("24", "24"): "24-bit K and V (f16 + bf8 residual)"}.get(
-        (opts.get("kv_k_bits", "16"), opts.get("kv_v_bits", "16")), "f16")
-    out = {
-        "metric": "decode tokens/sec", "value": tok_s, "unit": "tokens/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong" if use_tp else "weak", "vs_baseline": None,
-        "dtype": f"bf16 weights, {kv_desc} KV cache, bf16x2(hi+lo)/f16 MFMA operands, f32 accumulate",
-        "data": "synthetic",
-        "config": {"workload": f"{a.model} decode, {a.batch} live sequences, prompts U[{a.prompt_min},{a.prompt_max}] seed {a.seed}",
-                   **({"options": list(a.option)} if a.option else {}),
-                   "batch": a.batch, "global_batch": a.batch * replicas, "mean_context": round(mean_ctx, 1),
-                   "parallelism": f"tp{world}" if use_tp else (f"dp{world} x tp1 (independent replicas, no collective)" if world > 1 else "tp1")},
-        "roofline": roof,
-        "step_roofline": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": step_gbs / HBM_PEAK_GBS, "bytes_per_step": bytes_total / a.steps,
-                          "event_ms_per_step": ev_ms / a.steps},
-        "kernel_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
-    }
+    out["roofline"] = roof
+    out["kernel_ms_per_step"] = {k: round(v, 4) for k, v in per_step.items()}
     if a.profile_meta:
         # for tools/summarize_prof.py: the attention kernel's algorithmic bytes per launch averaged over ALL decode steps of
         # this process (warm-up + timed + per-kernel pass) -- the launches a rocprofv3 --stats average covers

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 # the driver's own command (round-end bench: --gpus 1 --steps 20 --warmup 5); the profiled passes run the SAME decode steps
 # (warm-up 5 + timed 20 + the per-kernel HIP-event pass), so one bytes-per-launch figure holds for the line, the kernel
 # stats and the counter pass
-D="--gpus 1 --steps 20 --warmup 5"
+D="--gpus 1 --steps 20 --warmup 5 --full"  # --full: the roofline, per-kernel and all_decode_steps figures are behind it
 timeout -k 10 700 python3 $R/bench.py $D > $R/gpurun_out/bench_$TAG.log 2>&1 || exit 1
 tail -1 $R/gpurun_out/bench_$TAG.log | cut -c1-200
 B="python3 $R/bench.py --no-cpu-baseline --skip-tp-leg --profile-meta --no-live-traffic"
