@@ -114,6 +114,12 @@ int nvllm_tp_shard(const nvllm_qwen3_config* cfg, int tp_size, int tp_rank, cons
  *      max_batched_tokens bounds the rows processed per internal chunk (prefill is chunked). */
 int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, int max_seqs, int max_batched_tokens);
 int nvllm_kv_num_free_blocks(const nvllm_model* m);
+/* Width of the K/V cache elements, 16 (f16, the default) or 24 bits each: a 24-bit element is the f16 value plus one e5m2
+ * byte holding its rounding residual (13..14 significant bits, cache bytes x1.5), which every attention kernel -- prefill,
+ * decode, the fused QKV epilogue -- reads and writes natively.  24-bit V is what holds the 1e-3 logits bar on
+ * heavy-tailed checkpoints; 24-bit K comes only together with 24-bit V; both need head_dim 128 (every Qwen3 size).
+ * Takes effect at the next nvllm_kv_alloc.  NVLLM_EINVAL at once for any other combination. */
+int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_bits);
 /* bytes one cached token occupies on this rank (K+V, all layers) */
 int64_t nvllm_kv_bytes_per_token(const nvllm_model* m);
 /* release a sequence's blocks (call where the reference calls BlockManager::deallocate,
@@ -183,6 +189,9 @@ int nvllm_op_rope(nvllm_ctx* ctx, float* q, float* k, int B, int nh, int kv, int
  * cache and runs the same paged kernel the step path uses. */
 int nvllm_op_attention(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
                        int T, int hd, float scale, float* out);
+/* ... with the scratch cache k_bits / v_bits wide (16 or 24 each, the combinations nvllm_model_set_kv_cache_bits takes) */
+int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
+                          int T, int hd, float scale, int k_bits, int v_bits, float* out);
 
 /* embedding gather  src/models/qwen3.rs:465-468: table [V,H] f32 (device), ids [n] u32 (device) */
 int nvllm_op_embedding(nvllm_ctx* ctx, const float* table, const uint32_t* ids, int n, int V, int H, float* y);

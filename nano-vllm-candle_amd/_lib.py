@@ -60,6 +60,7 @@ _SIGS = {
     "nvllm_model_weight_bytes": (C.c_int64, [_vp]),
     "nvllm_tp_shard": (C.c_int, [C.POINTER(Qwen3ConfigC), C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
     "nvllm_kv_alloc": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nvllm_model_set_kv_cache_bits": (C.c_int, [_vp, C.c_int, C.c_int]),
     "nvllm_kv_num_free_blocks": (C.c_int, [_vp]),
     "nvllm_kv_bytes_per_token": (C.c_int64, [_vp]),
     "nvllm_seq_free": (C.c_int, [_vp, C.c_int64]),
@@ -85,6 +86,7 @@ _SIGS = {
     "nvllm_op_silu_mul": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _fp]),
     "nvllm_op_rope": (C.c_int, [_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "nvllm_op_attention": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
+    "nvllm_op_attention_kv": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _fp]),
     "nvllm_op_embedding": (C.c_int, [_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "nvllm_op_argmax": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _fp]),
     "nvllm_op_allreduce": (C.c_int, [_vp, _fp, C.c_int64]),

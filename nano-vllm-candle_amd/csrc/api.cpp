@@ -80,6 +80,14 @@ static int fail(nvllm_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
+// K/V cache widths: 16 or 24 bits each; 24-bit K only beside 24-bit V; the 24-bit kernels are head_dim 128 (every Qwen3 size)
+static int check_kv_cache_bits(nvllm_ctx* ctx, int k_bits, int v_bits, int hd) {
+    if ((k_bits != 16 && k_bits != 24) || (v_bits != 16 && v_bits != 24)) return fail(ctx, NVLLM_EINVAL, "K/V cache bits are 16 or 24");
+    if (k_bits == 24 && v_bits != 24) return fail(ctx, NVLLM_EINVAL, "a 24-bit K cache needs a 24-bit V cache as well");
+    if (v_bits == 24 && hd != 128) return fail(ctx, NVLLM_EINVAL, "the 24-bit K/V cache needs head_dim 128 (have %d)", hd);
+    return NVLLM_OK;
+}
+
 #define HIPCHK(ctx, expr)                                                                              \
     do {                                                                                               \
         hipError_t e_ = (expr);                                                                        \
@@ -504,6 +512,8 @@ struct nvllm_model {
     bool stamps_on = false;
     int stamp_launch = 0;
     int64_t tile_launches = 0;  // projections run by the tile GEMM so far (tests assert the path they force was taken)
+    int64_t tile_qkv_fused_launches = 0;  // ... QKV projections among them with the fused norm + RoPE + KV-write epilogue
+    int64_t attn_prefill_launches = 0;    // launches of the LDS-staged prefill attention kernel
 
     // per-kernel-class HIP-event timing (bench roofline leg); 0 = off
     int prof_kind = 0;
@@ -1247,7 +1257,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         }
         PROF(m, PROF_EMPTY, hipSuccess);  // calibration: an event pair around nothing, at the attention launch's place
         STAMPS(aa, m);
-        if (qt == 2 && !aa.kv.vlo) PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s));
+        if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // o_proj (+ residual + post-attention norm prep; qwen3.rs:278, :393)
         int rc = row_linear(fp.o, w.o, m->ctxh, m->ctxl, KO, w.ln2, m->ssqA, packed);
@@ -1350,8 +1360,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     const int o_ks = tile_on ? gemm_tile_splits(R, H, KO, tmin, max_ks) : 0, d_ks = tile_on ? gemm_tile_splits(R, H, m->I_l, tmin, max_ks) : 0;
     const int q_ks = tile_on ? gemm_tile_splits(R, NQ, H, tmin, max_ks) : 0;
     const bool t_qkv = q_ks > 0 && (size_t)q_ks * R * NQ <= m->slab_floats;
-    // (the fused epilogue writes V as packed f16 stores only: 24-bit V keeps the row kernel)
-    const bool t_qkv_fused = t_qkv && m->opt_tile_fuse_qk && m->vlocache.empty() && gemm_tile_qkv_ok(R, NQ, H, hd, tmin);
+    const bool t_qkv_fused = t_qkv && m->opt_tile_fuse_qk && gemm_tile_qkv_ok(R, NQ, H, hd, tmin);
     const bool t_o = o_ks > 0 && (size_t)o_ks * R * H <= m->slab_floats;
     const bool t_gu = tile_on && gemm_tile_ok(R, 2 * m->I_l, H, 2, tmin);
     const bool t_down = t_gu && m->I_l % 32 == 0 && d_ks > 0 && (size_t)d_ks * R * H <= m->slab_floats;
@@ -1381,6 +1390,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         if (t_qkv_fused && !fuse_qk) {
             // prompt chunk: q/k-norm + RoPE + KV write + q output in the QKV GEMM's epilogue (one wave tile = one head)
             PROF(m, PROF_GEMM, launch_gemm_tile_qkv(m->xh, m->xl, w.qkv, R, qa, tmin, s));
+            ++m->tile_qkv_fused_launches;
         } else {
             if (t_qkv) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.qkv, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &qa.n_slabs, s));
             else rcg = gemm_slabs(m, m->xh, m->xl, H, w.qkv, m->slabs, R, 8, &qa.n_slabs, packed);
@@ -1404,7 +1414,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
             parts_max = m->attn_parts_max;
         }
         STAMPS(aa, m);
-        if (qt == 2 && !aa.kv.vlo) PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s));
+        if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // output projection (qwen3.rs:278) + TP all-reduce
         int o_slabs = 1;
@@ -1735,7 +1745,7 @@ static int step_impl(nvllm_model* m, int n_seqs, const int64_t* seq_ids, const u
             p.tile_row0.push_back(r); p.tile_nrows.push_back(e - r); p.tile_slot.push_back(p.slot[r]);
             // prefill attention shares K/V between the four q-tiles of a workgroup: a sequence's tiles start on a multiple
             // of four, its last group is padded with empty tiles
-            if (qt == 2 && m->vlocache.empty() && (e == r0 + R || row_seq[e] != row_seq[r]))
+            if (qt == 2 && (e == r0 + R || row_seq[e] != row_seq[r]))
                 while (p.tile_row0.size() % kPrefillTileGroup) { p.tile_row0.push_back(r); p.tile_nrows.push_back(0); p.tile_slot.push_back(p.slot[r]); }
             r = e;
         }
@@ -1885,11 +1895,21 @@ extern "C" int64_t nvllm_last_step_bytes(const nvllm_model* m) { return m ? m->l
 // gate/up, down per layer).  The product library returns NVLLM_ESTATE.
 // tuning switches of a model (A/B and tests): "stream_combine" = the streaming GEMM's in-launch split-K combine;
 // "tile_min_wgs" = smallest grid the prefill tile GEMM is used for (1: whenever the shape fits; 0: never)
+extern "C" int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_bits) {
+    if (!m) return NVLLM_EINVAL;
+    int rc = check_kv_cache_bits(m->ctx, k_bits, v_bits, m->hd);
+    if (rc) return rc;
+    m->opt_kv_k_bits = k_bits;  // read by the next nvllm_kv_alloc
+    m->opt_kv_v_bits = v_bits;
+    return NVLLM_OK;
+}
+
 extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int value) {
     if (!m || !name) return NVLLM_EINVAL;
     if (!strcmp(name, "stream_combine")) { m->opt_stream_combine = value; return NVLLM_OK; }
     if (!strcmp(name, "oneshot_allreduce")) { m->opt_oneshot_allreduce = value; return NVLLM_OK; }  // takes effect at the next kv_alloc
     if (!strcmp(name, "oneshot_spins")) { m->opt_oneshot_spins = std::max(1, value); return NVLLM_OK; }
+    // kv_k_bits / kv_v_bits: the debug spelling of nvllm_model_set_kv_cache_bits (nvllm_amd.h), one width at a time
     if (!strcmp(name, "kv_k_bits")) {  // takes effect at the next kv_alloc (which insists on kv_v_bits = 24 with it)
         if (value != 16 && value != 24) return fail(m->ctx, NVLLM_EINVAL, "kv_k_bits is 16 or 24");
         m->opt_kv_k_bits = value; return NVLLM_OK;
@@ -1909,11 +1929,15 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
 }
 
 // counters for tests: "oneshot_calls" = all-reduces this model's context has run on the one-shot device path;
-// "tile_gemm_launches" = projections this model has run on the prefill tile GEMM
+// "tile_gemm_launches" = projections this model has run on the prefill tile GEMM; "tile_qkv_fused_launches" = QKV
+// projections among them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of
+// the LDS-staged prefill attention kernel
 extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value) {
     if (!m || !name || !value) return NVLLM_EINVAL;
     if (!strcmp(name, "oneshot_calls")) { *value = (int64_t)m->ctx->os_calls; return NVLLM_OK; }
     if (!strcmp(name, "tile_gemm_launches")) { *value = m->tile_launches; return NVLLM_OK; }
+    if (!strcmp(name, "tile_qkv_fused_launches")) { *value = m->tile_qkv_fused_launches; return NVLLM_OK; }
+    if (!strcmp(name, "attn_prefill_launches")) { *value = m->attn_prefill_launches; return NVLLM_OK; }
     if (!strcmp(name, "kv_f16_saturated") || !strcmp(name, "kv_f16_absmax_bits")) {
         // scan of the whole K/V pool (debug, off the hot path): elements the f16_sat clamp of a cache write produced, and the
         // largest magnitude stored (f16 bits; 0x7BFF = 65504 is the clamp)
@@ -2116,8 +2140,16 @@ extern "C" int nvllm_op_rope(nvllm_ctx* ctx, float* q, float* k, int B, int nh, 
 
 extern "C" int nvllm_op_attention(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
                                   int T, int hd, float scale, float* out) {
+    return nvllm_op_attention_kv(ctx, q, k, v, B, nh, kv, T, hd, scale, 16, 16, out);
+}
+
+// ... with the scratch cache in the given width (16 or 24 bits per K / V element: f16 + one e5m2 residual byte)
+extern "C" int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
+                                     int T, int hd, float scale, int k_bits, int v_bits, float* out) {
     if (!ctx || !q || !k || !v || !out || B < 1 || T < 1) return fail(ctx, NVLLM_EINVAL, "bad attention arguments");
     if (hd != 64 && hd != 128) return fail(ctx, NVLLM_EINVAL, "head_dim %d unsupported (64 or 128)", hd);
+    int rcb = check_kv_cache_bits(ctx, k_bits, v_bits, hd);
+    if (rcb) return rcb;
     if (nh % kv || nh / kv > 16) return fail(ctx, NVLLM_EINVAL, "bad GQA shape");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -2135,6 +2167,14 @@ extern "C" int nvllm_op_attention(nvllm_ctx* ctx, const float* q, const float* k
     HIPCHK(ctx, t.get(&kvl.v, cache_elems));
     HIPCHK(ctx, hipMemsetAsync(kvl.k, 0, cache_elems * 2, s));
     HIPCHK(ctx, hipMemsetAsync(kvl.v, 0, cache_elems * 2, s));
+    if (v_bits == 24) {
+        HIPCHK(ctx, t.get(&kvl.vlo, cache_elems));
+        HIPCHK(ctx, hipMemsetAsync(kvl.vlo, 0, cache_elems, s));
+    }
+    if (k_bits == 24) {
+        HIPCHK(ctx, t.get(&kvl.klo, cache_elems));
+        HIPCHK(ctx, hipMemsetAsync(kvl.klo, 0, cache_elems, s));
+    }
     const int qt = 2, tpt = attn_tokens_per_tile(gqa, qt);
     std::vector<int> hpos(rows), hslot(rows), hbt(nblk), ht0, htn, hts;
     for (int b = 0; b < B; ++b) {

@@ -29,10 +29,13 @@ __device__ __forceinline__ _Float16 f16_sat(float x) { return (_Float16)fminf(fm
 // 24-bit V (opt-in): beside the f16 value the cache keeps the rounding residual r = x - f16(x) as the TOP BYTE
 // of f16(r) -- a bf8 / e5m2 number (sign, 5 exponent bits, 2 mantissa bits), rounded to nearest even.  |r| <= ulp/2, so the
 // pair carries 13..14 significant bits; the attention kernels feed the bytes to a bf8 MFMA as they are.
-
-// 24-bit V (opt-in): beside the f16 value the cache keeps the rounding residual r = x - f16(x) as the TOP BYTE
-// of f16(r) -- an e5m2 number (sign, 5 exponent bits, 2 mantissa bits), rounded to nearest even.  |r| <= ulp/2, so the pair
-// carries 13..14 significant bits, and the reader rebuilds r's f16 by a byte shift (no arithmetic).
+// The ONE rounding every cache writer uses (row kernel, decode prologue, tile-GEMM epilogue write byte-identical caches):
+// x clamped to +-65504, h = its f16, the residual taken as f16 and its top byte rounded to nearest even.
+__device__ __forceinline__ uint32_t kv24_residual(float x, _Float16 h) {
+    const float xc = fminf(fmaxf(x, -65504.f), 65504.f);
+    const uint32_t b = __builtin_bit_cast(uint16_t, (_Float16)(xc - (float)h));
+    return ((b + 0x7Fu + ((b >> 8) & 1u)) >> 8) & 0xFFu;
+}
 __device__ __forceinline__ void store_v24(_Float16* v, uint8_t* vlo, int t_in_block, int d, int hd, float x);
 
 // max of three without the canonicalising v_max_f32 x, x that fmaxf() adds per operand (operands here are MFMA results
@@ -147,11 +150,7 @@ __device__ __forceinline__ size_t vlo_packed_offset(int t_in_block, int d, int h
 __device__ __forceinline__ void store_v24(_Float16* v, uint8_t* vlo, int t_in_block, int d, int hd, float x) {
     const _Float16 h = f16_sat(x);
     v[v_packed_offset(t_in_block, d, hd)] = h;
-    if (vlo) {
-        const float xc = fminf(fmaxf(x, -65504.f), 65504.f);
-        const uint32_t b = __builtin_bit_cast(uint16_t, (_Float16)(xc - (float)h));
-        vlo[vlo_packed_offset(t_in_block, d, hd)] = (uint8_t)((b + 0x7Fu + ((b >> 8) & 1u)) >> 8);
-    }
+    if (vlo) vlo[vlo_packed_offset(t_in_block, d, hd)] = (uint8_t)kv24_residual(x, h);
 }
 
 // 24-bit K (KvLayout::klo): the same residual byte per K element, two QK^T fragments (head-dim chunks c, c+1 of one 16-token
@@ -164,11 +163,7 @@ __device__ __forceinline__ size_t klo_packed_offset(int t_in_block, int d, int h
 __device__ __forceinline__ void store_k24(_Float16* k, uint8_t* klo, int t_in_block, int d, int hd, float x) {
     const _Float16 h = f16_sat(x);
     k[k_packed_offset(t_in_block, d, hd)] = h;
-    if (klo) {
-        const float xc = fminf(fmaxf(x, -65504.f), 65504.f);
-        const uint32_t b = __builtin_bit_cast(uint16_t, (_Float16)(xc - (float)h));
-        klo[klo_packed_offset(t_in_block, d, hd)] = (uint8_t)((b + 0x7Fu + ((b >> 8) & 1u)) >> 8);
-    }
+    if (klo) klo[klo_packed_offset(t_in_block, d, hd)] = (uint8_t)kv24_residual(x, h);
 }
 
 typedef const __attribute__((address_space(1))) void* gptr_t;

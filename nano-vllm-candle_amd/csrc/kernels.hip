@@ -2119,11 +2119,52 @@ __global__ void __launch_bounds__(NWV * 64, QT == 1 ? 2 : 1) attn_paged_kernel(A
 // order so the image is lane-linear -- and read from LDS by the waves that still need it (causal: wave w stops after the
 // tile that holds its last token); the next tile is in flight while the current one is consumed.  The decode kernel,
 // which prefill used before, had every wave fetch its own K/V tiles from global memory: no reuse across q-tiles.
+//
+// VLO (as in attn_paged_kernel; head_dim 128 only): 1 = 24-bit V, 2 = 24-bit K and V.  The residual planes are laid out
+// for 1 KiB wave-loads, so a tile simply grows by four fragments per plane: V's (one per PAIR of PV fragments), then K's
+// (two per 16-token half, one per pair of head-dim chunks); TILE_FRAGS 16 / 20 / 24 = 4 / 5 / 6 DMA loads per wave and
+// 48 / 60 / 72 KiB of ring, still two workgroups per CU.  The residual bytes are bf8 numbers and go to a bf8 MFMA as they
+// are, against q (once) and P (per tile) converted to bf8.  This loop is MFMA/VALU-bound, so the f16-MFMA <-> bf8-MFMA
+// SrcC hazard (mfma_result_settled) is kept out of it where it can be and paid once where it cannot:
+//   * Q.K^T: the score accumulators start at zero every tile, so the tile's 2 x QT x DC bf8 MFMAs (K residuals) run
+//     FIRST, all of them, then ONE fence over the 2 x QT score accumulators, then the f16 MFMAs.  bf8 accumulators of
+//     their own, added by the VALU before the softmax, need no fence at all but 16 more registers while q (hi, lo, bf8)
+//     and O are live: that build came out at 256 registers plus 40 bytes of scratch, and its 16 v_add per tile cost the
+//     VALU -- the unit that sets this loop's time -- what the fence costs in wait states another wave can fill.
+//   * P.V: O must take both.  V fragments are walked in the pairs that share a residual slot: the pair's 4 x QT f16
+//     MFMAs, ONE 20-wait-state fence over the pair's 2 x QT accumulators, the pair's 2 x QT bf8 MFMAs.  Tiles of odd
+//     index run the same pair bf8-first -- an even tile leaves O as a bf8 result, which a bf8 MFMA may take at once, and
+//     an odd tile leaves it as an f16 result for the even tile's f16 MFMAs -- so every accumulator changes MFMA type once
+//     per tile, not twice: DT / 2 = 4 fences per wave and tile, each behind 8 MFMAs that do not depend on it.  (A wave
+//     walks tiles 0 .. my_last without gaps, so the parity of kt is the parity of its own tile count.)
 // ---------------------------------------------------------------------------------------------------
-template <int HD, int QT>
+// one wait for up to four accumulators that change MFMA type together (see mfma_result_settled)
+__device__ __forceinline__ void mfma_results_settled(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+// f32 x 8 (as two f16x4 halves of an MFMA operand) -> 8 bf8 bytes
+__device__ __forceinline__ long bf8x8_of(const f16x8& x) {
+    int w0 = 0, w1 = 0;
+    w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)x[0], (float)x[1], w0, false);
+    w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)x[2], (float)x[3], w0, true);
+    w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)x[4], (float)x[5], w1, false);
+    w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)x[6], (float)x[7], w1, true);
+    return (long)(((unsigned long long)(unsigned)w1 << 32) | (unsigned)w0);
+}
+// the 8 residual bytes of fragment `odd` (0 / 1) of a 16-byte residual slot
+__device__ __forceinline__ long resid_half(const uint4& p, int odd) {
+    return (long)(odd ? ((unsigned long long)p.w << 32) | p.z : ((unsigned long long)p.y << 32) | p.x);
+}
+
+template <int HD, int QT, int VLO = 0>
 __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
+    static_assert(VLO == 0 || (HD == 128 && QT == 2), "the 24-bit cache is served for head_dim 128");
     constexpr int DC = HD / 32, DT = HD / 16, NWV = 4;
-    constexpr int TILE_FRAGS = 2 * DC + DT;  // 1 KiB fragments of one 32-token K/V tile: K lo half, K hi half, V
+    constexpr bool KLO = VLO == 2;
+    constexpr int DL = VLO ? DT / 2 : 0;              // V residual fragments of a tile (two PV fragments each)
+    constexpr int FV = 2 * DC, FVL = FV + DT, FKL = FVL + DL;  // first fragment of V, of V's residuals, of K's residuals
+    constexpr int TILE_FRAGS = FKL + (KLO ? DC : 0);  // 1 KiB fragments of one 32-token K/V tile: K lo half, K hi half, V [, V res.][, K res.]
+    static_assert(TILE_FRAGS % NWV == 0, "every wave issues the same number of DMA loads per tile");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     uint4* lds = reinterpret_cast<uint4*>(smem_raw);  // [3 stages][TILE_FRAGS][64]
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2193,11 +2234,28 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
         const int T0 = kt << 5, tb = T0 & 255;
         const _Float16* kb = kbase + (size_t)(blk * kv_l + kh) * kBlockTokens * HD + (size_t)(tb >> 4) * (DC * 512) + lane * 8;
         const _Float16* vb = vbase + (size_t)(blk * kv_l + kh) * kBlockTokens * HD + (size_t)(tb >> 5) * (DT * 512) + lane * 8;
+        if constexpr (VLO == 0) {
 #pragma unroll
-        for (int i = 0; i < TILE_FRAGS / NWV; ++i) {
-            const int f = wave + i * NWV;
-            const _Float16* src = f < 2 * DC ? kb + f * 512 : vb + (f - 2 * DC) * 512;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + (size_t)(buf * TILE_FRAGS + f) * 64), 16, 0, 0);
+            for (int i = 0; i < TILE_FRAGS / NWV; ++i) {
+                const int f = wave + i * NWV;
+                const _Float16* src = f < 2 * DC ? kb + f * 512 : vb + (f - 2 * DC) * 512;
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + (size_t)(buf * TILE_FRAGS + f) * 64), 16, 0, 0);
+            }
+        } else {
+            // residual planes: a 32-token tile's bytes of one kv head are DL (V) resp. DC (K) contiguous 1 KiB fragments at
+            // tile * 4 KiB of the (block, kv head) slab of kBlockTokens x HD bytes -- same block id as the f16 fragments
+            const size_t ro = (size_t)(blk * kv_l + kh) * kBlockTokens * HD + (size_t)(tb >> 5) * (DL * 1024) + lane * 16;
+            const uint8_t* vlb = a.kv.vlo + ro;
+            const uint8_t* klb = KLO ? a.kv.klo + ro : vlb;
+#pragma unroll
+            for (int i = 0; i < TILE_FRAGS / NWV; ++i) {
+                // every plane's fragment count is a multiple of NWV: load i of all four waves reads ONE plane, known here
+                static_assert(FV % NWV == 0 && FVL % NWV == 0 && FKL % NWV == 0, "a DMA round never straddles two planes");
+                const int f = wave + i * NWV;
+                const void* src = i * NWV < FV ? (const void*)(kb + f * 512) : i * NWV < FVL ? (const void*)(vb + (f - FV) * 512)
+                                : i * NWV < FKL ? (const void*)(vlb + (f - FVL) * 1024) : (const void*)(klb + (f - FKL) * 1024);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + (size_t)(buf * TILE_FRAGS + f) * 64), 16, 0, 0);
+            }
         }
     };
     // ring of three stages: tile kt+2 is issued right after the barrier that opens tile kt, so a tile has two
@@ -2209,8 +2267,10 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
     if (wg_last >= 1) stage(1, 1, blk_b);
     int blk_pf = blk_load(2);
     f16x8 qh[QT][DC], ql[QT][DC];
+    // 24-bit K: q once more as bf8, the B operand of the residual MFMA (two mantissa bits leave that 2^-12-sized term 12 % accurate)
+    [[maybe_unused]] long q8[QT][DC];
 #pragma unroll
-    for (int t = 0; t < QT; ++t)
+    for (int t = 0; t < QT; ++t) {
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
             float x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2225,7 +2285,11 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
                 qh[t][c][j] = h;
                 ql[t][c][j] = (_Float16)(x[j] - (float)h);
             }
+            if constexpr (KLO) q8[t][c] = bf8x8_of(qh[t][c]);
         }
+        // one sub-tile's q rows in flight at a time: with all 16 loads hoisted beside q in three formats the K+V build spilled
+        if constexpr (VLO != 0) __builtin_amdgcn_sched_barrier(0);
+    }
     f32x4 o[QT][DT];
     float m[QT], lsum[QT];
 #pragma unroll
@@ -2260,6 +2324,24 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
         f32x4 sa[QT], sb[QT];
 #pragma unroll
         for (int t = 0; t < QT; ++t) { sa[t] = f32x4{0.f, 0.f, 0.f, 0.f}; sb[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        if constexpr (KLO) {
+            // K residuals x q in bf8 FIRST, into the fresh score accumulators; one fence, then the f16 MFMAs add to them
+            // (header comment).  One 16-byte slot = head-dim chunks c, c + 1 of one 16-token half.
+#pragma unroll
+            for (int c2 = 0; c2 < DC / 2; ++c2) {
+                const uint4 pa = lds[(size_t)(buf * TILE_FRAGS + FKL + c2) * 64 + lane];
+                const uint4 pb = lds[(size_t)(buf * TILE_FRAGS + FKL + DC / 2 + c2) * 64 + lane];
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) {
+                        sa[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(resid_half(pa, e), q8[t][2 * c2 + e], sa[t], 0, 0, 0);
+                        sb[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(resid_half(pb, e), q8[t][2 * c2 + e], sb[t], 0, 0, 0);
+                    }
+            }
+            mfma_results_settled(sa[0], sa[1], sb[0], sb[1]);
+            __builtin_amdgcn_sched_barrier(0);  // the f16 fragments' LDS reads stay behind the fence (registers)
+        }
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
             const f16x8 fa = __builtin_bit_cast(f16x8, lds[(size_t)(buf * TILE_FRAGS + c) * 64 + lane]);
@@ -2271,6 +2353,7 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
                 sb[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, qh[t][c], sb[t], 0, 0, 0);
                 sb[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, ql[t][c], sb[t], 0, 0, 0);
             }
+            if constexpr (KLO) __builtin_amdgcn_sched_barrier(0);  // two chunks' fragments in flight at most (registers)
         }
         // Online softmax, written for the VALU: this block, not the MFMAs, set the kernel's time (30 of 45 us per launch
         // as first written).  Raw v_exp_f32 (arguments are <= 0, a flushed denormal is 0 either way; exp2f() costs a
@@ -2327,26 +2410,87 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
                     o[t][d][0] *= alpha[t]; o[t][d][1] *= alpha[t]; o[t][d][2] *= alpha[t]; o[t][d][3] *= alpha[t];
                 }
         }
+        if constexpr (VLO == 0) {
 #pragma unroll
-        for (int d = 0; d < DT; ++d) {
-            const f16x8 fv = __builtin_bit_cast(f16x8, lds[(size_t)(buf * TILE_FRAGS + 2 * DC + d) * 64 + lane]);
+            for (int d = 0; d < DT; ++d) {
+                const f16x8 fv = __builtin_bit_cast(f16x8, lds[(size_t)(buf * TILE_FRAGS + 2 * DC + d) * 64 + lane]);
 #pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, P[t], o[t][d], 0, 0, 0);
-                o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, Pl[t], o[t][d], 0, 0, 0);
+                for (int t = 0; t < QT; ++t) {
+                    o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, P[t], o[t][d], 0, 0, 0);
+                    o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, Pl[t], o[t][d], 0, 0, 0);
+                }
             }
+        } else {
+            // P once more as bf8: the B operand of the V-residual MFMA (decode kernel: 2^-15 of V left of that term)
+            long P8[QT];
+#pragma unroll
+            for (int t = 0; t < QT; ++t) P8[t] = bf8x8_of(P[t]);
+            // one pair of PV fragments (one residual slot) at a time; BF8_FIRST on tiles of odd index (header comment)
+            auto pv_pairs = [&](auto bf8_first_c) {
+                constexpr bool BF8_FIRST = decltype(bf8_first_c)::value;
+#pragma unroll
+                for (int d2 = 0; d2 < DT / 2; ++d2) {
+                    const uint4 pr = lds[(size_t)(buf * TILE_FRAGS + FVL + d2) * 64 + lane];
+                    auto resid = [&]() {
+#pragma unroll
+                        for (int e = 0; e < 2; ++e)
+#pragma unroll
+                            for (int t = 0; t < QT; ++t)
+                                o[t][2 * d2 + e] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(resid_half(pr, e), P8[t], o[t][2 * d2 + e], 0, 0, 0);
+                    };
+                    if constexpr (BF8_FIRST) {
+                        resid();
+                        mfma_results_settled(o[0][2 * d2], o[1][2 * d2], o[0][2 * d2 + 1], o[1][2 * d2 + 1]);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const f16x8 fv = __builtin_bit_cast(f16x8, lds[(size_t)(buf * TILE_FRAGS + FV + 2 * d2 + e) * 64 + lane]);
+#pragma unroll
+                        for (int t = 0; t < QT; ++t) {
+                            o[t][2 * d2 + e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, P[t], o[t][2 * d2 + e], 0, 0, 0);
+                            o[t][2 * d2 + e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, Pl[t], o[t][2 * d2 + e], 0, 0, 0);
+                        }
+                    }
+                    if constexpr (!BF8_FIRST) {
+                        mfma_results_settled(o[0][2 * d2], o[1][2 * d2], o[0][2 * d2 + 1], o[1][2 * d2 + 1]);
+                        resid();
+                    }
+                    // keep the next pairs' LDS reads on their side: hoisted over the fences they held 40 registers more
+                    // than the 16-bit loop's and the K+V build spilled
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            if (kt & 1) pv_pairs(std::true_type{});
+            else pv_pairs(std::false_type{});
         }
     }
     NVLLM_STAMP(a, 2);
+    // 24-bit builds: the store's row / head / lane-group indices are worked out again from an opaque copy of the lane id, so
+    // that nothing of the epilogue's addressing stays live across the loop (it was spilled there: 254+ registers)
+    int o_row[QT], o_head = my_head, o_grp = grp;
+#pragma unroll
+    for (int t = 0; t < QT; ++t) o_row[t] = my_row[t];
+    if constexpr (VLO != 0) {
+        int le = lane;
+        asm volatile("" : "+v"(le));
+        const int l15e = le & 15;
+        o_grp = le >> 4;
+        o_head = kh * gqa + (l15e % gqa);
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int tok = t * tpq + l15e / gqa;
+            o_row[t] = (l15e < tpq * gqa) && (tok < nrows) ? row0 + tok : -1;
+        }
+    }
     // every wave owns its rows for the whole context: normalise and store (D[dim 4*grp+reg][q row l15] -> out[row][head dims])
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         float l = lsum[t];
         l += __shfl_xor(l, 16);
         l += __shfl_xor(l, 32);
-        if (my_row[t] < 0) continue;
+        if (o_row[t] < 0) continue;
         const float inv = 1.0f / l;
-        const size_t base = (size_t)my_row[t] * ldq + (size_t)my_head * HD + grp * 4;
+        const size_t base = (size_t)o_row[t] * ldq + (size_t)o_head * HD + o_grp * 4;
 #pragma unroll
         for (int d = 0; d < DT; ++d) {
             const float y0 = o[t][d][0] * inv, y1 = o[t][d][1] * inv, y2 = o[t][d][2] * inv, y3 = o[t][d][3] * inv;
@@ -2354,7 +2498,7 @@ __global__ void __launch_bounds__(256, 2) attn_prefill_kernel(AttnArgs a) {
             if (a.out_hi) {
                 uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
                 split_bf16(y0, h0, l0); split_bf16(y1, h1, l1); split_bf16(y2, h2, l2); split_bf16(y3, h3, l3);
-                const size_t xo = a.out_packed ? xpack_off(my_row[t], my_head * HD + d * 16 + grp * 4, ldq >> 5) : base + d * 16;
+                const size_t xo = a.out_packed ? xpack_off(o_row[t], o_head * HD + d * 16 + o_grp * 4, ldq >> 5) : base + d * 16;
                 *reinterpret_cast<uint2*>(a.out_hi + xo) = make_uint2(h0 | ((uint32_t)h1 << 16), h2 | ((uint32_t)h3 << 16));
                 *reinterpret_cast<uint2*>(a.out_lo + xo) = make_uint2(l0 | ((uint32_t)l1 << 16), l2 | ((uint32_t)l3 << 16));
             }
@@ -2425,11 +2569,23 @@ static hipError_t attn_launch_t(const AttnArgs& a, int n_tiles, int grid_z, hipS
 }
 
 // prefill: n_tiles (a multiple of 4: every sequence's tile list padded with empty tiles) q-tiles of 2 sub-tiles each
+template <int VLO>
+static hipError_t attn_prefill_launch_v(const AttnArgs& a, dim3 grid, hipStream_t s) {
+    const size_t lds = (size_t)3 * (16 + 4 * VLO) * 1024;  // 48 / 60 / 72 KiB; past 64 KiB the dynamic-LDS limit must be raised
+    static std::atomic<uint64_t> lds_set{0};
+    ensure_dyn_lds(reinterpret_cast<const void*>(attn_prefill_kernel<128, 2, VLO>), lds, lds_set);
+    attn_prefill_kernel<128, 2, VLO><<<grid, 256, lds, s>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t launch_attn_prefill(const AttnArgs& a, int n_tiles, hipStream_t s) {
     if (n_tiles <= 0) return hipSuccess;
-    if (a.kv.vlo) return hipErrorNotSupported;  // 24-bit V: the caller runs prompt chunks through attn_paged_kernel<.., 2, ..>
+    if (a.kv.klo && !a.kv.vlo) return hipErrorInvalidValue;  // 24-bit K comes with 24-bit V only
+    if (a.kv.vlo && a.kv.hd != 128) return hipErrorNotSupported;  // the 24-bit cache is served for head_dim 128 (every Qwen3 size)
     if (n_tiles % 4 || a.gqa < 1 || a.gqa > 16 || (a.kv.hd != 128 && a.kv.hd != 64)) return hipErrorInvalidValue;
     dim3 grid((n_tiles / 4) * a.kv.kv_l);
+    if (a.kv.klo) return attn_prefill_launch_v<2>(a, grid, s);
+    if (a.kv.vlo) return attn_prefill_launch_v<1>(a, grid, s);
     if (a.kv.hd == 128) {
         const size_t lds = (size_t)3 * (2 * 4 + 8) * 1024;
         attn_prefill_kernel<128, 2><<<grid, 256, lds, s>>>(a);

@@ -23,6 +23,9 @@
 // RoPE), half-split RoPE (rotary_embedding.rs:82-107: features d and d+64 sit in the same lane, accumulators j and j+4),
 // then q (scaled) to the f32 q buffer, K and V as f16 into the paged cache in their fragment orders.  No f32 QKV
 // round trip through HBM and no separate row kernel.
+// MODE 4 / 5: MODE 3 for a 24-bit V / 24-bit K and V cache (KvLayout::vlo / klo): the epilogue also writes the residual byte
+// of every cache element, rounded exactly as store_v24 / store_k24 round it.  In both residual planes the four elements a
+// lane (K) or an LDS word (V) holds are four CONSECUTIVE bytes, so each f16x4 store gets one 4-byte store beside it.
 #include <algorithm>
 
 #include "device_common.h"
@@ -65,6 +68,8 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
     constexpr int FRW = WN * NTW;          // 1 KiB fragments per stage: W ...
     constexpr int FR = FRW + 2 * XT;       // ... then [plane][row tile] of x
     constexpr int NI = (FR + 7) / 8;       // DMA wave-copies per wave per stage
+    constexpr bool QKV = MODE >= 3 && MODE <= 5;  // fused QKV epilogue; V24 / K24: it writes the residual planes too
+    [[maybe_unused]] constexpr bool V24 = MODE == 4 || MODE == 5, K24 = MODE == 5;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     uint4* lds = reinterpret_cast<uint4*>(smem_raw);
     const int lane = threadIdx.x & 63;
@@ -85,11 +90,11 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
     }
     const int mtiles = (a.M + 15) >> 4;
     NVLLM_STAMP(a, 0);
-    // MODE 3: position and cache block of this lane's four tokens, fetched NOW (two dependent loads each) so that they
+    // QKV modes: position and cache block of this lane's four tokens, fetched NOW (two dependent loads each) so that they
     // land under the K loop; in the epilogue they were 8 us of latency chain per workgroup (stamps)
     [[maybe_unused]] int e_pos[4], e_blk[4], e_slot0 = 0;
     [[maybe_unused]] bool e_one_seq = true;  // this lane's four tokens belong to one sequence
-    if constexpr (MODE == 3) {
+    if constexpr (QKV) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int rowc = min(mb * (WM * 64) + wm * 64 + b * 16 + l15, a.M - 1);
@@ -110,7 +115,7 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
         if (f < FRW) {
             // MODE 3: the block's two heads are nb and NB + nb, not neighbours: a V head (whose epilogue is scattered
             // 2-byte cache stores) then always shares its workgroup with a q head, and the V tail spreads over twice the CUs
-            const int ntile = MODE == 3 ? (f < NTW ? nb : a.NB + nb) * NTW + f % NTW : nb * FRW + f;
+            const int ntile = QKV ? (f < NTW ? nb : a.NB + nb) * NTW + f % NTW : nb * FRW + f;
             src[i] = a.wp + ((size_t)ntile * a.KT + kt0) * 64;
         } else {
             const int g = f - FRW, plane = g / XT, mt = min(mb * XT + (g % XT), mtiles - 1);
@@ -236,8 +241,8 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
                 }
             }
         }
-    } else if constexpr (MODE == 3) {
-        static_assert(MODE != 3 || (NTW == 8 && WN == 2), "one wave tile = one 128-wide head");
+    } else if constexpr (QKV) {
+        static_assert(!QKV || (NTW == 8 && WN == 2), "one wave tile = one 128-wide head");
         const QkvArgs& q = a.q;
         const int hh = wn == 0 ? nb : a.NB + nb;  // this wave's head: [q heads | k heads | v heads]
         const int nh = q.nh_l, kvl = q.kv.kv_l;
@@ -257,6 +262,9 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
             if (nvalid > 0 && __builtin_amdgcn_ballot_w64(!okl) == 0) {
                 constexpr int LDV = 72;  // halves per feature row: 64 tokens + 3 shift, padded to a multiple of 4
                 _Float16* vt = reinterpret_cast<_Float16*>(smem_raw) + (size_t)wm * (128 * LDV);
+                // 24-bit V: the residual bytes as Vr[feature][token + pos % 4] behind the four Vt images (72 + 36 KiB of the
+                // 144 KiB ring): an aligned group of four positions is one 4-byte word, consecutive in vlo_packed_offset
+                [[maybe_unused]] uint8_t* vr = reinterpret_cast<uint8_t*>(smem_raw) + (size_t)WM * (128 * LDV * 2) + (size_t)wm * (128 * LDV);
                 const int sh = P0 & 3;
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
@@ -264,7 +272,12 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) vt[(j * 16 + grp * 4 + r) * LDV + b * 16 + l15 + sh] = f16_sat(acc[j][b][r] * ri);
+                        for (int r = 0; r < 4; ++r) {
+                            const float x = acc[j][b][r] * ri;
+                            const _Float16 h = f16_sat(x);
+                            vt[(j * 16 + grp * 4 + r) * LDV + b * 16 + l15 + sh] = h;
+                            if constexpr (V24) vr[(j * 16 + grp * 4 + r) * LDV + b * 16 + l15 + sh] = (uint8_t)kv24_residual(x, h);
+                        }
                 }
                 const int blkA = __builtin_amdgcn_readfirstlane(e_blk[0]);                       // block of position P0
                 const int blkB = __builtin_amdgcn_readlane(e_blk[(nvalid - 1) >> 4], (nvalid - 1) & 15);  // ... of the last valid token
@@ -275,6 +288,7 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
                     const int p = P0 + tfirst;       // multiple of 4
                     const int blk = (p >> 8) == (P0 >> 8) ? blkA : blkB;
                     _Float16* vdst = reinterpret_cast<_Float16*>(q.kv.v) + (size_t)(blk * kvl + kvh) * kBlockTokens * 128;
+                    [[maybe_unused]] uint8_t* rdst = V24 ? q.kv.vlo + (size_t)(blk * kvl + kvh) * kBlockTokens * 128 : nullptr;
                     const int tib = p & 255, tile32 = tib >> 5, tt = tib & 31;
                     const bool full = tfirst >= 0 && tfirst + 3 < nvalid;
 #pragma unroll
@@ -289,6 +303,17 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
                                 if (tfirst + i >= 0 && tfirst + i < nvalid) reinterpret_cast<uint16_t*>(vdst)[off + i] = hv[i];
+                        }
+                        if constexpr (V24) {
+                            const uint32_t rw = *reinterpret_cast<const uint32_t*>(vr + d * LDV + 4 * cq);
+                            const size_t roff = vlo_packed_offset(tib, d, 128);  // tib is a multiple of 4: bytes roff .. roff + 3
+                            if (full) {
+                                *reinterpret_cast<uint32_t*>(rdst + roff) = rw;
+                            } else {
+#pragma unroll
+                                for (int i = 0; i < 4; ++i)
+                                    if (tfirst + i >= 0 && tfirst + i < nvalid) rdst[roff + i] = (uint8_t)(rw >> (8 * i));
+                            }
                         }
                     }
                 }
@@ -341,12 +366,18 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
                         for (int j = 0; j < 8; ++j)
                             *reinterpret_cast<float4*>(qo + j * 16) = make_float4(acc[j][b][0], acc[j][b][1], acc[j][b][2], acc[j][b][3]);
                     } else {
-                        _Float16* k = reinterpret_cast<_Float16*>(q.kv.k) + (size_t)(e_blk[b] * kvl + (hh - nh)) * kBlockTokens * 128;
+                        const size_t ko = (size_t)(e_blk[b] * kvl + (hh - nh)) * kBlockTokens * 128;
+                        _Float16* k = reinterpret_cast<_Float16*>(q.kv.k) + ko;
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
                             typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
                             const f16x4 v = {f16_sat(acc[j][b][0]), f16_sat(acc[j][b][1]), f16_sat(acc[j][b][2]), f16_sat(acc[j][b][3])};
                             *reinterpret_cast<f16x4*>(k + k_packed_offset(pos & 255, j * 16 + grp * 4, 128)) = v;
+                            if constexpr (K24) {  // features 16j + 4grp .. + 3: byte j' = d & 7 of one 8-byte fragment half
+                                const uint32_t rw = kv24_residual(acc[j][b][0], v[0]) | (kv24_residual(acc[j][b][1], v[1]) << 8) |
+                                                    (kv24_residual(acc[j][b][2], v[2]) << 16) | (kv24_residual(acc[j][b][3], v[3]) << 24);
+                                *reinterpret_cast<uint32_t*>(q.kv.klo + ko + klo_packed_offset(pos & 255, j * 16 + grp * 4, 128)) = rw;
+                            }
                         }
                     }
                 }
@@ -367,11 +398,15 @@ __global__ void __launch_bounds__(512) gemm_tile_kernel(TileArgs a) {
                 if (row < a.M) {
                     const float ri = rownorm_rinv(q.rn, row);
                     const int pos = e_pos[b];
-                    _Float16* v = reinterpret_cast<_Float16*>(q.kv.v) + (size_t)(e_blk[b] * kvl + (hh - nh - kvl)) * kBlockTokens * 128;
+                    const size_t vo = (size_t)(e_blk[b] * kvl + (hh - nh - kvl)) * kBlockTokens * 128;
+                    _Float16* v = reinterpret_cast<_Float16*>(q.kv.v) + vo;
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[v_packed_offset(pos & 255, j * 16 + grp * 4 + r, 128)] = f16_sat(acc[j][b][r] * ri);
+                        for (int r = 0; r < 4; ++r) {
+                            if constexpr (V24) store_v24(v, q.kv.vlo + vo, pos & 255, j * 16 + grp * 4 + r, 128, acc[j][b][r] * ri);
+                            else v[v_packed_offset(pos & 255, j * 16 + grp * 4 + r, 128)] = f16_sat(acc[j][b][r] * ri);
+                        }
                 }
             }
         }
@@ -491,6 +526,9 @@ hipError_t launch_gemm_tile_qkv(const bf16_bits* xh, const bf16_bits* xl, const 
     TileArgs a;
     a.xh = reinterpret_cast<const uint4*>(xh); a.xl = reinterpret_cast<const uint4*>(xl); a.wp = w.data;
     a.M = M; a.N = w.N; a.KT = w.K / 32; a.q = qa;
+    if (qa.kv.klo && !qa.kv.vlo) return hipErrorInvalidValue;  // 24-bit K comes with 24-bit V only
+    if (qa.kv.klo) return tile_launch_t<8, 2, 5>(a, 1, s);
+    if (qa.kv.vlo) return tile_launch_t<8, 2, 4>(a, 1, s);
     return tile_launch_t<8, 2, 3>(a, 1, s);
 }
 

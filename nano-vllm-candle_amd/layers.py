@@ -255,13 +255,15 @@ class SiluAndMul:
 class Attention:
     """The attention `layers::Attention` names (src/layers/attention.rs:4-16 is a dead sdpa wrapper): causal GQA
     attention with the live path's math (src/models/qwen3.rs:236-277).  forward(q [B,nh,T,hd], k, v [B,kv,T,hd])
-    -> ctx [B*T, nh*hd].  softcapping must be 0 (the live path has none)."""
+    -> ctx [B*T, nh*hd].  softcapping must be 0 (the live path has none).  kv_bits = (k_bits, v_bits): width of the
+    scratch K/V cache the op runs on, 16 or 24 bits each (Qwen3ForCausalLM.set_kv_cache_bits)."""
 
-    def __init__(self, num_heads, head_dim, scale, softcapping=0.0, ctx=None):
+    def __init__(self, num_heads, head_dim, scale, softcapping=0.0, ctx=None, kv_bits=(16, 16)):
         if softcapping not in (0, 0.0, 1.0):
             raise ValueError("softcapping is not part of the reference's live attention path")
         self.num_heads, self.head_dim, self.scale, self.softcapping = num_heads, head_dim, float(scale), softcapping
         self.ctx = ctx or default_context()
+        self.kv_bits = (int(kv_bits[0]), int(kv_bits[1]))
 
     def forward(self, q, k, v):
         q, k, v = _f32(q), _f32(k), _f32(v)
@@ -271,7 +273,8 @@ class Attention:
             raise ValueError("shape mismatch in attention")
         ctx = self.ctx
         dq, dk, dv, do = ctx.to_device(q), ctx.to_device(k), ctx.to_device(v), ctx.empty((B * T, nh * hd))
-        _lib.check(_lib.lib().nvllm_op_attention(ctx.h, dq.ptr, dk.ptr, dv.ptr, B, nh, kv, T, hd, self.scale, do.ptr), ctx.h)
+        _lib.check(_lib.lib().nvllm_op_attention_kv(ctx.h, dq.ptr, dk.ptr, dv.ptr, B, nh, kv, T, hd, self.scale,
+                                                    self.kv_bits[0], self.kv_bits[1], do.ptr), ctx.h)
         return do.numpy()
 
     __call__ = forward

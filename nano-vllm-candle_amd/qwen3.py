@@ -198,6 +198,11 @@ class Qwen3ForCausalLM:
         _lib.check(_lib.lib().nvllm_model_finalize(self.h), self.ctx.h)
 
     # ---- KV pool ----
+    def set_kv_cache_bits(self, k_bits, v_bits):
+        """Width of the K / V cache elements for the NEXT kv_alloc: 16 (f16) or 24 (f16 + an e5m2 residual byte) each;
+        24-bit K only together with 24-bit V, and head_dim 128.  Anything else raises NvllmError (EINVAL)."""
+        _lib.check(_lib.lib().nvllm_model_set_kv_cache_bits(self.h, int(k_bits), int(v_bits)), self.ctx.h)
+
     def kv_alloc(self, num_blocks, max_seqs, max_batched_tokens=4096, block_size=256):
         _lib.check(_lib.lib().nvllm_kv_alloc(self.h, num_blocks, block_size, max_seqs, max_batched_tokens), self.ctx.h)
         self._kv = True
