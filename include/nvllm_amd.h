@@ -120,6 +120,15 @@ int nvllm_kv_num_free_blocks(const nvllm_model* m);
  * heavy-tailed checkpoints; 24-bit K comes only together with 24-bit V; both need head_dim 128 (every Qwen3 size).
  * Takes effect at the next nvllm_kv_alloc.  NVLLM_EINVAL at once for any other combination. */
 int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_bits);
+/* How the decode attention kernel's work is split over workgroups.  NVLLM_ATTN_PER_SEQUENCE (the default): one workgroup
+ * per (sequence, kv head), whatever the sequence's context.  NVLLM_ATTN_BALANCED: the 32-token K/V tiles of all sequences,
+ * longest context first, are cut into spans of equal length, one workgroup per (span, kv head); a sequence that several
+ * spans share is merged inside the same launch by whichever of them finishes last, in span order, so results do not
+ * depend on timing.  Served for head_dim 128 and decode steps (one new token per sequence); any other step runs the
+ * default schedule.  Takes effect at the next step.  NVLLM_EINVAL at once for any other value. */
+#define NVLLM_ATTN_PER_SEQUENCE 0
+#define NVLLM_ATTN_BALANCED 1
+int nvllm_model_set_attention_schedule(nvllm_model* m, int schedule);
 /* bytes one cached token occupies on this rank (K+V, all layers) */
 int64_t nvllm_kv_bytes_per_token(const nvllm_model* m);
 /* release a sequence's blocks (call where the reference calls BlockManager::deallocate,

@@ -38,6 +38,10 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
  *   "stream_combine" (default 0): let the fused forward use the streaming GEMM's in-launch split-K combine epilogues (fewer
  *       launches; measured slower on MI355X than slabs + a consumer launch);
  *   "tile_min_wgs" (default 192; 0 never, 1 whenever the shape fits), "tile_fuse_qk" (default 1): the prefill tile GEMM;
+ *   "attn_balanced" (0 | 1; from the next step on): the debug spelling of nvllm_model_set_attention_schedule (nvllm_amd.h);
+ *   "attn_balanced_wgs" (default 0): spans (workgroups) per kv head of the balanced schedule; 0 = two workgroups per CU over
+ *       the local kv heads; positive values are for tests and tuning, clamped to what nvllm_kv_alloc sized the partial
+ *       buffers for (four times the automatic value);
  *   "no_fused", "no_xpack", "no_rowpar", "no_attn_prologue" (default 0): force the generic decode path / row-major planes /
  *       no whole-K row-parallel GEMMs / q,k-norm + RoPE + KV write in their own row kernel. */
 int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
@@ -45,7 +49,8 @@ int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
 /* counters for tests: "oneshot_calls" = all-reduces run on the one-shot device path by this model's context;
  * "tile_gemm_launches" = projections run by the prefill tile GEMM; "tile_qkv_fused_launches" = QKV projections among
  * them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of the LDS-staged
- * prefill attention kernel (one per layer and prompt chunk, whatever the cache width); "kv_f16_saturated" = elements of the K/V pool at the
+ * prefill attention kernel (one per layer and prompt chunk, whatever the cache width); "attn_balanced_launches" = launches
+ * of the work-balanced decode attention kernel (one per layer and decode step that qualifies); "kv_f16_saturated" = elements of the K/V pool at the
  * f16 clamp (every cache write saturates at +-65504; a scan of the pool, off the hot path); "kv_f16_absmax_bits" = the
  * largest magnitude the pool holds, as f16 bits */
 int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value);

@@ -61,6 +61,7 @@ _SIGS = {
     "nvllm_tp_shard": (C.c_int, [C.POINTER(Qwen3ConfigC), C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
     "nvllm_kv_alloc": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nvllm_model_set_kv_cache_bits": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "nvllm_model_set_attention_schedule": (C.c_int, [_vp, C.c_int]),
     "nvllm_kv_num_free_blocks": (C.c_int, [_vp]),
     "nvllm_kv_bytes_per_token": (C.c_int64, [_vp]),
     "nvllm_seq_free": (C.c_int, [_vp, C.c_int64]),
@@ -106,7 +107,7 @@ _SIGS = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _DEBUG_EXPORTS_ADDED_LATER = ("nvllm_debug_stamps", "nvllm_debug_stamps_read", "nvllm_ctx_create_null_comm", "nvllm_debug_set_option",
-                              "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter")
+                              "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter", "nvllm_model_set_attention_schedule")
 
 _lib = None
 

@@ -484,6 +484,14 @@ struct nvllm_model {
     uint32_t* d_next = nullptr;
     float *attn_po = nullptr, *attn_pml = nullptr;  // split-KV partials [max_seqs][nh_l][kAttnMaxParts][hd] / [..][2]
     int attn_part_tiles = 4, attn_parts_max = 1;   // this step's split geometry (decode only)
+    // work-balanced decode attention (opt-in, nvllm_model_set_attention_schedule): AttnBalance buffers, sized at kv_alloc
+    int opt_attn_schedule = NVLLM_ATTN_PER_SEQUENCE;
+    int opt_attn_balanced_wgs = 0;  // spans per kv head; 0 = two workgroups per CU over the local kv heads
+    int bal_auto_spans = 1;         // that automatic value, from the device's CU count
+    AttnBalance bal;
+    bool bal_on = false;            // the chunk in flight runs the balanced schedule (its plan is on the device)
+    int bal_spans = 1;
+    int64_t attn_balanced_launches = 0;
     float* part_val = nullptr;  // fused LM-head arg-max partials [V_l/16][max_seqs]
     int* part_idx = nullptr;
     unsigned long long* argmax_scratch = nullptr;  // ticket + per-row keys of argmax_parts_kernel
@@ -627,10 +635,12 @@ static void free_kv(nvllm_model* m) {
     m->kcache.clear(); m->vcache.clear(); m->vlocache.clear(); m->klocache.clear();
     void* ptrs[] = {m->d_block_tables, m->d_ids, m->d_pos, m->d_slot, m->d_tile_row0, m->d_tile_nrows, m->d_tile_slot,
                     m->d_last_rows, m->d_tile_order, m->d_tile_last, m->d_group_order, m->resid, m->slabs, m->qbuf, m->logits, m->d_maxval, m->red, m->xh, m->xl, m->xh2, m->xl2, m->ctxh, m->ctxl, m->ssqA, m->ssqB, m->d_next,
-                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps};
+                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     m->d_block_tables = nullptr; m->d_ids = nullptr; m->d_pos = m->d_slot = m->d_tile_row0 = m->d_tile_nrows = m->d_tile_slot = m->d_last_rows = m->d_tile_order = m->d_tile_last = m->d_group_order = nullptr;
     m->resid = m->slabs = m->qbuf = m->logits = m->d_maxval = m->red = nullptr; m->xh = m->xl = m->xh2 = m->xl2 = m->ctxh = m->ctxl = nullptr; m->ssqA = m->ssqB = nullptr; m->d_next = nullptr; m->part_val = nullptr; m->part_idx = nullptr; m->argmax_scratch = nullptr; m->attn_po = m->attn_pml = nullptr;
+    m->bal = AttnBalance();
+    m->bal_on = false;
     m->tap_h = m->tap_res = nullptr; m->cosv = m->sinv = nullptr; m->tickets = nullptr; m->qkv_out = nullptr; m->d_keys = nullptr; m->d_temps = nullptr;
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     m->h_stage = nullptr;
@@ -953,6 +963,20 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
     if (!rc) rc = dmalloc(ctx, &m->d_next, (size_t)max_seqs * (ctx->tp_size + 1));
     if (!rc) rc = dmalloc(ctx, &m->attn_po, (size_t)max_seqs * m->nh_l * kAttnMaxParts * m->hd);
     if (!rc) rc = dmalloc(ctx, &m->attn_pml, (size_t)max_seqs * m->nh_l * kAttnMaxParts * 2);
+    {
+        // balanced schedule: a span leaves at most two partials, so the storage goes with the workgroups, not with rows x parts;
+        // room for four times the automatic span count ("attn_balanced_wgs" is clamped to it)
+        int cus = 0;
+        HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        m->bal_auto_spans = std::max(1, (2 * std::max(1, cus) + m->kv_l - 1) / m->kv_l);
+        m->bal.max_rows = max_seqs;
+        m->bal.max_spans = 4 * m->bal_auto_spans;
+        if (!rc) rc = dmalloc(ctx, &m->bal.plan, attn_plan_ints(max_seqs, m->bal.max_spans));
+        if (!rc) rc = dmalloc(ctx, &m->bal.tickets, (size_t)max_seqs * m->kv_l);
+        if (!rc) HIPCHK(ctx, hipMemsetAsync(m->bal.tickets, 0, (size_t)max_seqs * m->kv_l * sizeof(unsigned), ctx->stream));
+        if (!rc) rc = dmalloc(ctx, &m->bal.part_o, (size_t)2 * m->bal.max_spans * m->nh_l * m->hd);
+        if (!rc) rc = dmalloc(ctx, &m->bal.part_ml, (size_t)2 * m->bal.max_spans * m->nh_l * 2);
+    }
     // one partial per LM-head wave: at most V_l/16 n-tiles rounded up to whole workgroups (<= 8 waves each)
     if (!rc) rc = dmalloc(ctx, &m->part_val, (size_t)(m->V_l / 16 + 16) * max_seqs);
     if (!rc) rc = dmalloc(ctx, &m->part_idx, (size_t)(m->V_l / 16 + 16) * max_seqs);
@@ -1258,6 +1282,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         PROF(m, PROF_EMPTY, hipSuccess);  // calibration: an event pair around nothing, at the attention launch's place
         STAMPS(aa, m);
         if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
+        else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // o_proj (+ residual + post-attention norm prep; qwen3.rs:278, :393)
         int rc = row_linear(fp.o, w.o, m->ctxh, m->ctxl, KO, w.ln2, m->ssqA, packed);
@@ -1331,7 +1356,19 @@ static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, 
 }
 
 // rows R (ids/pos/slot/tiles already on the device), n_last rows listed in d_last_rows -> logits rows
+// Balanced schedule: does this chunk qualify, and if so put its plan on the device -- once, ahead of the layers.  The plan
+// is a function of the positions already there (uploaded, or advanced by launch_advance_decode): no host round trip.
+static int plan_attn_balanced(nvllm_model* m, int R, int n_tiles, int qt) {
+    m->bal_on = m->opt_attn_schedule == NVLLM_ATTN_BALANCED && qt == 1 && n_tiles == R && R <= m->bal.max_rows && m->hd == 128 &&
+                !m->opt_no_attn_prologue;
+    if (!m->bal_on) return NVLLM_OK;
+    m->bal_spans = std::min(m->bal.max_spans, m->opt_attn_balanced_wgs > 0 ? m->opt_attn_balanced_wgs : m->bal_auto_spans);
+    HIPCHK(m->ctx, launch_attn_plan(m->d_pos, m->d_tile_order, R, m->bal_spans, m->bal, m->ctx->stream));
+    return NVLLM_OK;
+}
+
 static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last, int logits_row0) {
+    { const int rcb = plan_attn_balanced(m, R, n_tiles, qt); if (rcb) return rcb; }
     FusedPlan fp;
     if (fused_plan(m, R, fp)) return forward_chunk_fused(m, fp, R, n_tiles, qt, n_last, logits_row0);
     nvllm_ctx* ctx = m->ctx;
@@ -1415,6 +1452,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         }
         STAMPS(aa, m);
         if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
+        else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // output projection (qwen3.rs:278) + TP all-reduce
         int o_slabs = 1;
@@ -1904,8 +1942,18 @@ extern "C" int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_b
     return NVLLM_OK;
 }
 
+extern "C" int nvllm_model_set_attention_schedule(nvllm_model* m, int schedule) {
+    if (!m) return NVLLM_EINVAL;
+    if (schedule != NVLLM_ATTN_PER_SEQUENCE && schedule != NVLLM_ATTN_BALANCED)
+        return fail(m->ctx, NVLLM_EINVAL, "attention schedule is NVLLM_ATTN_PER_SEQUENCE (0) or NVLLM_ATTN_BALANCED (1), not %d", schedule);
+    m->opt_attn_schedule = schedule;  // read by the next step
+    return NVLLM_OK;
+}
+
 extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int value) {
     if (!m || !name) return NVLLM_EINVAL;
+    if (!strcmp(name, "attn_balanced")) return nvllm_model_set_attention_schedule(m, value);  // the debug spelling (bench.py --option)
+    if (!strcmp(name, "attn_balanced_wgs")) { m->opt_attn_balanced_wgs = std::max(0, value); return NVLLM_OK; }  // spans per kv head, 0 = automatic
     if (!strcmp(name, "stream_combine")) { m->opt_stream_combine = value; return NVLLM_OK; }
     if (!strcmp(name, "oneshot_allreduce")) { m->opt_oneshot_allreduce = value; return NVLLM_OK; }  // takes effect at the next kv_alloc
     if (!strcmp(name, "oneshot_spins")) { m->opt_oneshot_spins = std::max(1, value); return NVLLM_OK; }
@@ -1931,13 +1979,14 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
 // counters for tests: "oneshot_calls" = all-reduces this model's context has run on the one-shot device path;
 // "tile_gemm_launches" = projections this model has run on the prefill tile GEMM; "tile_qkv_fused_launches" = QKV
 // projections among them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of
-// the LDS-staged prefill attention kernel
+// the LDS-staged prefill attention kernel; "attn_balanced_launches" = launches of the work-balanced decode attention kernel
 extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value) {
     if (!m || !name || !value) return NVLLM_EINVAL;
     if (!strcmp(name, "oneshot_calls")) { *value = (int64_t)m->ctx->os_calls; return NVLLM_OK; }
     if (!strcmp(name, "tile_gemm_launches")) { *value = m->tile_launches; return NVLLM_OK; }
     if (!strcmp(name, "tile_qkv_fused_launches")) { *value = m->tile_qkv_fused_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_prefill_launches")) { *value = m->attn_prefill_launches; return NVLLM_OK; }
+    if (!strcmp(name, "attn_balanced_launches")) { *value = m->attn_balanced_launches; return NVLLM_OK; }
     if (!strcmp(name, "kv_f16_saturated") || !strcmp(name, "kv_f16_absmax_bits")) {
         // scan of the whole K/V pool (debug, off the hot path): elements the f16_sat clamp of a cache write produced, and the
         // largest magnitude stored (f16 bits; 0x7BFF = 65504 is the clamp)

@@ -262,6 +262,28 @@ inline int attn_tokens_per_tile(int gqa, int qt) { return (16 / gqa) * qt; }
 constexpr int kPrefillTileGroup = 4;
 hipError_t launch_attn_prefill(const AttnArgs& a, int n_tiles, hipStream_t s);
 
+// ---- work-balanced decode attention (opt-in schedule; head_dim 128, fused prologue, one row per sequence) ----------
+// The 32-token K/V tiles of every sequence, longest context first (AttnArgs::tile_order), laid end to end and cut into
+// spans of equal tile count; one workgroup = one span x one kv head.  The plan is built on the device from the positions:
+//   plan[0] = tiles per span S, plan[1] = tiles in all, plan[2] = spans in use
+//   plan[4 + r]                  (r <= rows)  = first flat tile of the sequence of rank r (rank `rows`: the total)
+//   plan[4 + max_rows + 1 + w]   (w < spans)  = rank of the sequence that holds flat tile w * S
+// A span leaves at most two partials (m, l, un-normalised O per q head): slot 2w for its first segment, 2w + 1 for its
+// last; the last workgroup to draw a ticket on (row, kv head) merges that row's partials in span order.
+struct AttnBalance {
+    int* plan = nullptr;
+    int max_rows = 0, max_spans = 0;  // what the plan / partial buffers were sized for
+    unsigned* tickets = nullptr;      // [max_rows][kv_l], zero between launches
+    float* part_o = nullptr;          // [2 * max_spans][nh_l][hd]
+    float* part_ml = nullptr;         // [2 * max_spans][nh_l][2]
+};
+constexpr int kAttnSpanFloor = 4;  // fewest tiles per span: one per wave
+inline size_t attn_plan_ints(int max_rows, int max_spans) { return (size_t)4 + max_rows + 1 + max_spans; }
+// one small launch per decode step (not per layer): pos / order as in AttnArgs; spans = workgroups per kv head
+hipError_t launch_attn_plan(const int* pos, const int* order, int rows, int spans, const AttnBalance& b, hipStream_t s);
+// a: as for the fused decode launch_attn_paged (qkv != nullptr, tile_order set); the split-KV fields are not used
+hipError_t launch_attn_balanced(const AttnArgs& a, const AttnBalance& b, int rows, int spans, hipStream_t s);
+
 // ---- row-parallel projection with residual + next-norm epilogue (decode, tp == 1) ---------------------
 // resid_out = resid_in + x.W^T ; x' = next_w (.) resid_out as bf16 hi/lo ; ssq[group][row] partial sums of squares.
 // One workgroup owns 16 rows x (NWN*16) features for the WHOLE K (waves split K, reduced through LDS), all loads

@@ -2620,6 +2620,456 @@ hipError_t launch_attn_paged(const AttnArgs& a, int n_tiles, int qt, int rows, i
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Work-balanced decode attention (AttnBalance, kernels.h): one workgroup = one span of the flat tile list x one kv head.
+// The planner turns the step's positions into the span geometry once per step; the attention launches of all layers read it.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) attn_plan_kernel(const int* __restrict__ pos, const int* __restrict__ order, int rows, int spans,
+                                                        int* __restrict__ plan, int max_rows) {
+    __shared__ int part[256];
+    const int tid = threadIdx.x;
+    const int per = (rows + 255) / 256;
+    const int r0 = min(tid * per, rows), r1 = min(r0 + per, rows);  // this thread's ranks
+    int sum = 0;
+    for (int r = r0; r < r1; ++r) sum += (pos[order[r]] >> 5) + 1;
+    part[tid] = sum;
+    __syncthreads();
+    int base = 0, total = 0;
+    for (int i = 0; i < 256; ++i) {
+        const int v = part[i];
+        base += i < tid ? v : 0;
+        total += v;
+    }
+    const int S = max(kAttnSpanFloor, (total + spans - 1) / spans);
+    int* start = plan + 4;
+    int* span_rank0 = start + max_rows + 1;
+    if (tid == 0) {
+        plan[0] = S;
+        plan[1] = total;
+        plan[2] = (total + S - 1) / S;
+        start[rows] = total;
+    }
+    for (int r = r0; r < r1; ++r) {
+        const int n = (pos[order[r]] >> 5) + 1;
+        start[r] = base;
+        // spans that begin inside this sequence; w * S < total <= spans * S, so w < spans
+        for (int w = (base + S - 1) / S; w * S < base + n; ++w) span_rank0[w] = r;
+        base += n;
+    }
+}
+
+hipError_t launch_attn_plan(const int* pos, const int* order, int rows, int spans, const AttnBalance& b, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (!pos || !order || !b.plan || rows > b.max_rows || spans < 1 || spans > b.max_spans) return hipErrorInvalidValue;
+    attn_plan_kernel<<<1, 256, 0, s>>>(pos, order, rows, spans, b.plan, b.max_rows);
+    return hipGetLastError();
+}
+
+// The inner loop is attn_paged_kernel's decode form (QT 1, four waves, fused prologue): 1 KiB wave-loads straight to VGPRs,
+// two tile sets in flight per wave (one with a 24-bit cache), S^T = K.q^T and O^T += V^T.P on the 16x16x32 MFMAs with q
+// and P as f16 hi + lo, per-lane online softmax.  Around it the workgroup walks the (sequence, tile range) segments of its
+// span: prologue, tiles, four-wave reduction, then either the final output (the segment is the whole context) or a
+// partial and a ticket.  Nobody waits for another workgroup: the last arriver of a row merges, whoever that is.
+template <int HD, int VLO>
+__global__ void __launch_bounds__(256, 2) attn_balanced_kernel(AttnArgs a, AttnBalance b) {
+    constexpr int NWV = 4, DC = HD / 32, DT = HD / 16, DL = VLO ? DT / 2 : 1, half = HD / 2;
+    constexpr bool KLO = VLO == 2;
+    constexpr bool ONE_SET = VLO != 0;  // 24-bit cache: one tile set in flight per wave (a second needs > 256 registers)
+    constexpr int RL = DL + (KLO ? DC : 0);
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* ml = reinterpret_cast<float*>(smem_raw);                       // [NWV][2][16]
+    f32x4* obuf = reinterpret_cast<f32x4*>(smem_raw + NWV * 2 * 16 * 4);  // [NWV][DT][64]
+    unsigned* flag = reinterpret_cast<unsigned*>(smem_raw + NWV * 2 * 16 * 4 + NWV * DT * 64 * 16);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, grp = lane >> 4;
+    const int span = blockIdx.x, kh = blockIdx.y;
+    const int S = b.plan[0], total = b.plan[1];
+    const int* start = b.plan + 4;
+    const int* span_rank0 = start + b.max_rows + 1;
+    int f = span * S;
+    const int f_end = min(total, f + S);
+    if (f >= total) return;  // fewer tiles than spans x floor: this span is empty
+    int rank = span_rank0[span];
+    const int gqa = a.gqa, kv_l = a.kv.kv_l, ldq = a.nh_l * HD;
+    const bool valid = l15 < gqa;  // MFMA column l15 = q head kh * gqa + l15 of the segment's row
+    const int my_head = kh * gqa + (l15 % gqa);
+    const _Float16* kbase = reinterpret_cast<const _Float16*>(a.kv.k);
+    const _Float16* vbase = reinterpret_cast<const _Float16*>(a.kv.v);
+
+    for (int seg = 0; f < f_end; ++seg, ++rank) {
+        const int st = start[rank], en = start[rank + 1];
+        const int row = a.tile_order[rank];
+        const int pos = a.pos[row];
+        const int t_begin = f - st, t_end = min(en, f_end) - st, n_kv_tiles = en - st;
+        f = st + t_end;
+        const int my_pos = valid ? pos : -1;
+        const int* bt = a.block_tables + (size_t)a.tile_slot[row] * a.max_blocks;
+        // tile kt of this sequence if the segment holds it (kt < t_end), else the shared dummy tile: the same instruction
+        // stream with no K/V traffic, and no workgroup but the owner ever touches the tile of the new token
+        auto load_tile_or_dummy = [&](int kt, uint4 (&ka)[DC], uint4 (&kb2)[DC], uint4 (&vf)[DT], uint4 (&vl)[RL]) {
+            const bool real = kt < t_end;
+            const int T0 = min(kt, t_end - 1) << 5;
+            const int blk = bt[T0 >> 8], tb = T0 & 255;
+            const size_t slab = (size_t)(blk * kv_l + kh) * kBlockTokens * HD;
+            const _Float16* dummy = reinterpret_cast<const _Float16*>(g_attn_dummy_tile) + lane * 8;
+            const _Float16* kb = real ? kbase + slab + (size_t)(tb >> 4) * (DC * 512) + lane * 8 : dummy;
+            const _Float16* vb = real ? vbase + slab + (size_t)(tb >> 5) * (DT * 512) + lane * 8 : dummy;
+#pragma unroll
+            for (int c = 0; c < DC; ++c) {
+                ka[c] = ld_stream16(kb + c * 512);
+                kb2[c] = ld_stream16(kb + (DC + c) * 512);
+            }
+#pragma unroll
+            for (int d = 0; d < DT; ++d) vf[d] = ld_stream16(vb + d * 512);
+            if constexpr (VLO) {
+                const uint8_t* vlb = real ? a.kv.vlo + slab + (size_t)(tb >> 5) * (DL * 1024) + lane * 16
+                                          : reinterpret_cast<const uint8_t*>(g_attn_dummy_tile) + lane * 16;
+#pragma unroll
+                for (int d = 0; d < DL; ++d) vl[d] = ld_stream16(vlb + d * 1024);
+            }
+            if constexpr (KLO) {
+                const uint8_t* klb = real ? a.kv.klo + slab + (size_t)(tb >> 4) * ((DC / 2) * 1024) + lane * 16
+                                          : reinterpret_cast<const uint8_t*>(g_attn_dummy_tile) + lane * 16;
+#pragma unroll
+                for (int i = 0; i < DC; ++i) vl[DL + i] = ld_stream16(klb + i * 1024);
+            }
+        };
+
+        // ---- fused prologue (as attn_paged_kernel<.., FUSED>): sum the QKV slabs, deferred input norm, q/k RMSNorm + RoPE.
+        // Every workgroup of the row needs q; the one whose segment holds the new token's tile writes its K/V.
+        f16x8 qh[DC], ql[DC];
+        const float* qkv_row = a.qkv + (size_t)row * a.ldqkv;
+        const bool owner = (pos >> 5) >= t_begin && (pos >> 5) < t_end;
+        {
+            const int ln = min(lane, half - 1);
+            const float* pk = qkv_row + (size_t)(a.nh_l + kh) * HD;
+            const float* pv = qkv_row + (size_t)(a.nh_l + kv_l + kh) * HD;
+            float kx1 = 0.f, kx2 = 0.f, vx1 = 0.f, vx2 = 0.f, knw1 = 0.f, knw2 = 0.f, kc = 0.f, ks = 0.f;
+            if (wave == 0) {  // block-level branch: one wave produces the row's K/V for this kv head
+                kx1 = pk[ln]; kx2 = pk[ln + half]; vx1 = pv[ln]; vx2 = pv[ln + half];
+                knw1 = a.kn[ln]; knw2 = a.kn[ln + half];
+                kc = a.cos[(size_t)pos * half + ln]; ks = a.sin[(size_t)pos * half + ln];
+            }
+            float x[DC][8], qw[DC][8], cs[DC / 2][8], sn[DC / 2][8];
+            const float* pq = qkv_row + (size_t)(valid ? my_head : 0) * HD + grp * 8;
+#pragma unroll
+            for (int c = 0; c < DC; ++c) {
+                *reinterpret_cast<float4*>(&x[c][0]) = *reinterpret_cast<const float4*>(pq + c * 32);
+                *reinterpret_cast<float4*>(&x[c][4]) = *reinterpret_cast<const float4*>(pq + c * 32 + 4);
+                *reinterpret_cast<float4*>(&qw[c][0]) = *reinterpret_cast<const float4*>(a.qn + c * 32 + grp * 8);
+                *reinterpret_cast<float4*>(&qw[c][4]) = *reinterpret_cast<const float4*>(a.qn + c * 32 + grp * 8 + 4);
+            }
+#pragma unroll
+            for (int c = 0; c < DC / 2; ++c) {
+                const size_t o = (size_t)pos * half + c * 32 + grp * 8;
+                *reinterpret_cast<float4*>(&cs[c][0]) = *reinterpret_cast<const float4*>(a.cos + o);
+                *reinterpret_cast<float4*>(&cs[c][4]) = *reinterpret_cast<const float4*>(a.cos + o + 4);
+                *reinterpret_cast<float4*>(&sn[c][0]) = *reinterpret_cast<const float4*>(a.sin + o);
+                *reinterpret_cast<float4*>(&sn[c][4]) = *reinterpret_cast<const float4*>(a.sin + o + 4);
+            }
+            const float ssq_g = (a.rn.ssq && lane < a.rn.groups) ? a.rn.ssq[(size_t)lane * a.rn.stride + row] : 0.f;
+            const float ri = a.rn.ssq ? 1.0f / sqrtf(wave_sum(ssq_g) * a.rn.inv_h + a.rn.eps) : 1.0f;
+            for (int sl = 1; sl < a.n_slabs; ++sl) {  // split-K slabs of the generic path's QKV GEMM
+                const size_t so = (size_t)sl * a.slab_stride;
+                if (wave == 0) { kx1 += pk[so + ln]; kx2 += pk[so + ln + half]; vx1 += pv[so + ln]; vx2 += pv[so + ln + half]; }
+                float4 q0[DC][2];
+#pragma unroll
+                for (int c = 0; c < DC; ++c) {
+                    q0[c][0] = *reinterpret_cast<const float4*>(pq + so + c * 32);
+                    q0[c][1] = *reinterpret_cast<const float4*>(pq + so + c * 32 + 4);
+                }
+#pragma unroll
+                for (int c = 0; c < DC; ++c) {
+                    x[c][0] += q0[c][0].x; x[c][1] += q0[c][0].y; x[c][2] += q0[c][0].z; x[c][3] += q0[c][0].w;
+                    x[c][4] += q0[c][1].x; x[c][5] += q0[c][1].y; x[c][6] += q0[c][1].z; x[c][7] += q0[c][1].w;
+                }
+            }
+            if (wave == 0) {
+                const bool act = lane < half;
+                kx1 = act ? kx1 * ri : 0.f; kx2 = act ? kx2 * ri : 0.f;
+                const float kss = wave_sum(kx1 * kx1 + kx2 * kx2);
+                const float krinv = 1.0f / sqrtf(kss / (float)HD + a.eps);
+                if (owner && act) {
+                    const int blk = bt[pos >> 8];
+                    const float n1 = (kx1 * krinv) * knw1, n2 = (kx2 * krinv) * knw2;
+                    const size_t vo = (size_t)(blk * kv_l + kh) * kBlockTokens * HD;
+                    _Float16* k = reinterpret_cast<_Float16*>(a.kv.k) + vo;
+                    uint8_t* klo = KLO ? a.kv.klo + vo : nullptr;
+                    store_k24(k, klo, pos & 255, lane, HD, n1 * kc - n2 * ks);
+                    store_k24(k, klo, pos & 255, lane + half, HD, n2 * kc + n1 * ks);
+                    _Float16* v = reinterpret_cast<_Float16*>(a.kv.v) + vo;
+                    uint8_t* vlo = VLO ? a.kv.vlo + vo : nullptr;
+                    store_v24(v, vlo, pos & 255, lane, HD, vx1 * ri);
+                    store_v24(v, vlo, pos & 255, lane + half, HD, vx2 * ri);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            float ss = 0.f;
+#pragma unroll
+            for (int c = 0; c < DC; ++c)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    x[c][j] = valid ? x[c][j] * ri : 0.f;
+                    ss += x[c][j] * x[c][j];
+                }
+            ss += __shfl_xor(ss, 16);
+            ss += __shfl_xor(ss, 32);
+            const float rinv = 1.0f / sqrtf(ss / (float)HD + a.eps);
+#pragma unroll
+            for (int c = 0; c < DC / 2; ++c) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float n1 = (x[c][j] * rinv) * qw[c][j], n2 = (x[c + DC / 2][j] * rinv) * qw[c + DC / 2][j];
+                    const float y1 = (n1 * cs[c][j] - n2 * sn[c][j]) * a.q_scale;
+                    const float y2 = (n2 * cs[c][j] + n1 * sn[c][j]) * a.q_scale;
+                    const _Float16 h1 = (_Float16)y1, h2 = (_Float16)y2;
+                    qh[c][j] = h1;
+                    ql[c][j] = (_Float16)(y1 - (float)h1);
+                    qh[c + DC / 2][j] = h2;
+                    ql[c + DC / 2][j] = (_Float16)(y2 - (float)h2);
+                }
+            }
+        }
+        // The new token's K/V (wave 0 above) is visible from here on.  Nobody on this CU has touched that tile in this launch
+        // (only its owner ever reads it, and only behind this barrier); the agent-scope acquire makes that independent of
+        // who else shares the CU.  The barrier also separates the previous segment's LDS reads from this one's writes.
+        __syncthreads();
+        if (owner) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+
+        [[maybe_unused]] long q8[DC];
+        if constexpr (KLO) {
+#pragma unroll
+            for (int c = 0; c < DC; ++c) {
+                int w0 = 0, w1 = 0;
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[c][0], (float)qh[c][1], w0, false);
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[c][2], (float)qh[c][3], w0, true);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[c][4], (float)qh[c][5], w1, false);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[c][6], (float)qh[c][7], w1, true);
+                q8[c] = (long)(((unsigned long long)(unsigned)w1 << 32) | (unsigned)w0);
+            }
+        }
+        f32x4 o[DT];
+        float m = -1e30f, lsum = 0.f;
+#pragma unroll
+        for (int d = 0; d < DT; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        auto compute_tile = [&](int kt, const uint4 (&ka)[DC], const uint4 (&kb2)[DC], const uint4 (&vf)[DT], const uint4 (&vl)[RL]) {
+            const int T0 = kt << 5;
+            const int tokA = T0 + grp * 4, tokB = T0 + 16 + grp * 4;
+            f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < DC; ++c) {
+                const f16x8 fa = __builtin_bit_cast(f16x8, ka[c]);
+                const f16x8 fb = __builtin_bit_cast(f16x8, kb2[c]);
+                sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, qh[c], sa, 0, 0, 0);
+                sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, ql[c], sa, 0, 0, 0);
+                sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, qh[c], sb, 0, 0, 0);
+                sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, ql[c], sb, 0, 0, 0);
+                if constexpr (KLO) {  // the K residual bytes are bf8 numbers: A operands as they are
+                    const uint4 pa = vl[DL + (c >> 1)], pb = vl[DL + DC / 2 + (c >> 1)];
+                    const unsigned long long la = (c & 1) ? ((unsigned long long)pa.w << 32) | pa.z : ((unsigned long long)pa.y << 32) | pa.x;
+                    const unsigned long long lb = (c & 1) ? ((unsigned long long)pb.w << 32) | pb.z : ((unsigned long long)pb.y << 32) | pb.x;
+                    mfma_result_settled(sa);
+                    mfma_result_settled(sb);
+                    sa = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)la, q8[c], sa, 0, 0, 0);
+                    sb = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)lb, q8[c], sb, 0, 0, 0);
+                    mfma_result_settled(sa);  // ... and the next chunk's f16 MFMAs read these as SrcC
+                    mfma_result_settled(sb);
+                }
+            }
+            float mt = -1e30f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (tokA + r <= my_pos) mt = fmaxf(mt, sa[r]);
+                if (tokB + r <= my_pos) mt = fmaxf(mt, sb[r]);
+            }
+            mt = fmaxf(mt, __shfl_xor(mt, 16));
+            mt = fmaxf(mt, __shfl_xor(mt, 32));
+            const float mn = fmaxf(m, mt);
+            const float alpha = exp2f(m - mn);
+            m = mn;
+            f16x8 P, Pl;  // P as f16 hi + f16 lo (22 bits), see attn_paged_kernel
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pa = (tokA + r <= my_pos) ? exp2f(sa[r] - mn) : 0.f;
+                const float pb = (tokB + r <= my_pos) ? exp2f(sb[r] - mn) : 0.f;
+                ps += pa + pb;
+                P[r] = (_Float16)pa;
+                P[4 + r] = (_Float16)pb;
+                Pl[r] = (_Float16)(pa - (float)P[r]);
+                Pl[4 + r] = (_Float16)(pb - (float)P[4 + r]);
+            }
+            lsum = lsum * alpha + ps;
+            [[maybe_unused]] long P8 = 0;
+            if constexpr (VLO) {
+                int w0 = 0, w1 = 0;
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[0], (float)P[1], w0, false);
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[2], (float)P[3], w0, true);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[4], (float)P[5], w1, false);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[6], (float)P[7], w1, true);
+                P8 = (long)(((unsigned long long)(unsigned)w1 << 32) | (unsigned)w0);
+            }
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                f32x4 acc = o[d];
+                acc[0] *= alpha; acc[1] *= alpha; acc[2] *= alpha; acc[3] *= alpha;
+                const f16x8 fv = __builtin_bit_cast(f16x8, vf[d]);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, P, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, Pl, acc, 0, 0, 0);
+                if constexpr (VLO) {  // the V residual bytes against P in bf8
+                    const uint4 pr = vl[d >> 1];
+                    const unsigned long long lo8 = (d & 1) ? ((unsigned long long)pr.w << 32) | pr.z : ((unsigned long long)pr.y << 32) | pr.x;
+                    mfma_result_settled(acc);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)lo8, P8, acc, 0, 0, 0);
+                }
+                o[d] = acc;
+            }
+        };
+        {
+            // each wave takes every fourth tile of the segment; a set is refilled (two tiles ahead) right after it is consumed,
+            // unconditionally: past the segment's end the refill reads the dummy tile
+            uint4 kaA[DC], kbA[DC], vfA[DT], vlA[RL];
+            int kt = t_begin + wave;
+            load_tile_or_dummy(kt, kaA, kbA, vfA, vlA);
+            if constexpr (ONE_SET) {
+                while (kt < t_end) {
+                    compute_tile(kt, kaA, kbA, vfA, vlA);
+                    load_tile_or_dummy(kt + NWV, kaA, kbA, vfA, vlA);
+                    kt += NWV;
+                }
+            } else {
+                uint4 kaB[DC], kbB[DC], vfB[DT], vlB[RL];
+                load_tile_or_dummy(kt + NWV, kaB, kbB, vfB, vlB);
+                while (kt < t_end) {
+                    compute_tile(kt, kaA, kbA, vfA, vlA);
+                    load_tile_or_dummy(kt + 2 * NWV, kaA, kbA, vfA, vlA);
+                    kt += NWV;
+                    if (kt >= t_end) break;
+                    compute_tile(kt, kaB, kbB, vfB, vlB);
+                    load_tile_or_dummy(kt + 2 * NWV, kaB, kbB, vfB, vlB);
+                    kt += NWV;
+                }
+            }
+        }
+
+        // ---- the four waves' (m, l, O) through LDS, as attn_paged_kernel does
+        lsum += __shfl_xor(lsum, 16);
+        lsum += __shfl_xor(lsum, 32);
+        if (grp == 0) {
+            ml[(wave * 2 + 0) * 16 + l15] = m;
+            ml[(wave * 2 + 1) * 16 + l15] = lsum;
+        }
+        __syncthreads();
+        float ms = -1e30f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) ms = fmaxf(ms, ml[(w * 2 + 0) * 16 + l15]);
+        float ltot = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) ltot += ml[(w * 2 + 1) * 16 + l15] * exp2f(ml[(w * 2 + 0) * 16 + l15] - ms);
+        {
+            const float fs = exp2f(m - ms);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                o[d][0] *= fs; o[d][1] *= fs; o[d][2] *= fs; o[d][3] *= fs;
+                obuf[(wave * DT + d) * 64 + lane] = o[d];
+            }
+        }
+        __syncthreads();
+        const bool whole = t_begin == 0 && t_end == n_kv_tiles;  // uniform: the common case of a short sequence, no ticket
+        // partial slot of this segment: the span's first segment or its last (a middle one is always a whole context)
+        const size_t pslot = ((size_t)(2 * span + (seg ? 1 : 0)) * a.nh_l + my_head);
+        for (int d = wave; d < DT; d += NWV) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < NWV; ++w) {
+                const f32x4 v = obuf[(w * DT + d) * 64 + lane];
+                acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
+            }
+            if (!valid) continue;
+            if (!whole) {
+                *reinterpret_cast<float4*>(b.part_o + pslot * HD + d * 16 + grp * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                continue;
+            }
+            const float inv = 1.0f / ltot;
+            uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
+            split_bf16(acc[0] * inv, h0, l0); split_bf16(acc[1] * inv, h1, l1); split_bf16(acc[2] * inv, h2, l2); split_bf16(acc[3] * inv, h3, l3);
+            const int col = my_head * HD + d * 16 + grp * 4;
+            const size_t xo = a.out_packed ? xpack_off(row, col, ldq >> 5) : (size_t)row * ldq + col;
+            *reinterpret_cast<uint2*>(a.out_hi + xo) = make_uint2(h0 | ((uint32_t)h1 << 16), h2 | ((uint32_t)h3 << 16));
+            *reinterpret_cast<uint2*>(a.out_lo + xo) = make_uint2(l0 | ((uint32_t)l1 << 16), l2 | ((uint32_t)l3 << 16));
+        }
+        if (whole) continue;
+        if (wave == 0 && grp == 0 && valid) {
+            b.part_ml[pslot * 2 + 0] = ms;
+            b.part_ml[pslot * 2 + 1] = ltot;
+        }
+        // ---- publish the partial, draw a ticket on (row, kv head); the last arriver merges (stream_gemm.hip's protocol)
+        const int w0 = st / S, n_parts = (en - 1) / S - w0 + 1;  // the spans that hold a piece of this sequence
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            unsigned* ticket = b.tickets + (size_t)row * kv_l + kh;
+            const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned last = t == (unsigned)(n_parts - 1) ? 1u : 0u;
+            if (last) {
+                __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            *flag = last;
+        }
+        __syncthreads();
+        if (*flag == 0u) continue;  // uniform for the workgroup; the next segment's barriers order the flag's reuse
+        // merge in span order, this workgroup's own partial included: the sum must not depend on who arrived last.
+        // The sequence is its first span's first segment only if that span begins exactly where the sequence does.
+        const int slot0 = span_rank0[w0] == rank ? 0 : 1;
+        for (int item = threadIdx.x; item < gqa * (HD / 4); item += 256) {
+            const int head = kh * gqa + item / (HD / 4), c4 = (item % (HD / 4)) * 4;
+            float mm = -1e30f;
+            for (int p = 0; p < n_parts; ++p)
+                mm = fmaxf(mm, b.part_ml[((size_t)(2 * (w0 + p) + (p ? 0 : slot0)) * a.nh_l + head) * 2]);
+            float lt = 0.f;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int p = 0; p < n_parts; ++p) {
+                const size_t ps = (size_t)(2 * (w0 + p) + (p ? 0 : slot0)) * a.nh_l + head;
+                const float fp = exp2f(b.part_ml[ps * 2] - mm);
+                const float4 v = *reinterpret_cast<const float4*>(b.part_o + ps * HD + c4);
+                lt += b.part_ml[ps * 2 + 1] * fp;
+                acc.x += v.x * fp; acc.y += v.y * fp; acc.z += v.z * fp; acc.w += v.w * fp;
+            }
+            const float inv = 1.0f / lt;
+            uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
+            split_bf16(acc.x * inv, h0, l0); split_bf16(acc.y * inv, h1, l1); split_bf16(acc.z * inv, h2, l2); split_bf16(acc.w * inv, h3, l3);
+            const int col = head * HD + c4;
+            const size_t xo = a.out_packed ? xpack_off(row, col, ldq >> 5) : (size_t)row * ldq + col;
+            *reinterpret_cast<uint2*>(a.out_hi + xo) = make_uint2(h0 | ((uint32_t)h1 << 16), h2 | ((uint32_t)h3 << 16));
+            *reinterpret_cast<uint2*>(a.out_lo + xo) = make_uint2(l0 | ((uint32_t)l1 << 16), l2 | ((uint32_t)l3 << 16));
+        }
+    }
+}
+
+template <int VLO>
+static hipError_t attn_balanced_launch_v(const AttnArgs& a, const AttnBalance& b, int spans, hipStream_t s) {
+    const size_t lds = (size_t)4 * 2 * 16 * 4 + (size_t)4 * 8 * 64 * 16 + 16;
+    attn_balanced_kernel<128, VLO><<<dim3(spans, a.kv.kv_l), 256, lds, s>>>(a, b);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_balanced(const AttnArgs& a, const AttnBalance& b, int rows, int spans, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (a.kv.hd != 128 || a.gqa < 1 || a.gqa > 16 || !a.qkv || !a.tile_order || !a.out_hi || !a.out_lo) return hipErrorInvalidValue;
+    if (!b.plan || !b.tickets || !b.part_o || !b.part_ml || rows > b.max_rows || spans < 1 || spans > b.max_spans) return hipErrorInvalidValue;
+    if (a.kv.klo && !a.kv.vlo) return hipErrorInvalidValue;  // 24-bit K comes with 24-bit V only
+    if (a.kv.klo) return attn_balanced_launch_v<2>(a, b, spans, s);
+    if (a.kv.vlo) return attn_balanced_launch_v<1>(a, b, spans, s);
+    return attn_balanced_launch_v<0>(a, b, spans, s);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // SwiGLU gate: SiluAndMul::forward (activation.rs:13-18): split last dim in two, silu(a)*b
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) silu_mul_kernel(const float* __restrict__ gu, int n_slabs, int64_t slab_stride,

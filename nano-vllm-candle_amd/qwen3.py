@@ -203,6 +203,15 @@ class Qwen3ForCausalLM:
         24-bit K only together with 24-bit V, and head_dim 128.  Anything else raises NvllmError (EINVAL)."""
         _lib.check(_lib.lib().nvllm_model_set_kv_cache_bits(self.h, int(k_bits), int(v_bits)), self.ctx.h)
 
+    ATTENTION_SCHEDULES = {"per_sequence": 0, "balanced": 1}
+
+    def set_attention_schedule(self, schedule):
+        """How decode attention is split over workgroups, from the next step on: "per_sequence" (the default: one workgroup
+        per sequence and kv head) or "balanced" (equal spans of K/V tiles whatever the sequence boundaries, merged inside
+        the launch; head_dim 128, other steps keep the default).  Anything else raises NvllmError (EINVAL)."""
+        code = self.ATTENTION_SCHEDULES.get(schedule, schedule if isinstance(schedule, int) else -1)
+        _lib.check(_lib.lib().nvllm_model_set_attention_schedule(self.h, int(code)), self.ctx.h)
+
     def kv_alloc(self, num_blocks, max_seqs, max_batched_tokens=4096, block_size=256):
         _lib.check(_lib.lib().nvllm_kv_alloc(self.h, num_blocks, block_size, max_seqs, max_batched_tokens), self.ctx.h)
         self._kv = True
