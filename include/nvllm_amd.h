@@ -167,6 +167,20 @@ int nvllm_decode_next(nvllm_model* m, uint32_t* next_ids);
 int nvllm_decode_enqueue(nvllm_model* m);
 int nvllm_decode_collect(nvllm_model* m, uint32_t* next_ids);
 
+/* The fast path with sample_token: one more decode step for the batch of the previous step, whose ids are DRAWN as
+ * nvllm_step_sample draws them -- in the LM head's epilogue, so no logits are stored and, in a steady loop, nothing is copied
+ * to the device.  temperatures[i] belongs to sequence i of the previous step's batch (NULL: NVLLM_EINVAL).  The drawn id is
+ * what the next step is fed, on the device, as the greedy id is by nvllm_decode_next.
+ * Contract: next_ids equal what nvllm_step_sample returns for the same seed, temperatures and the sequences' full token
+ * lists, at every tp size the fast path serves (the draw is keyed by (seed, seq_id, position, global vocabulary id); a row
+ * with a NaN logit or a non-finite maximum -- exactly the rows whose softmax weights form no distribution -- takes the last
+ * maximal logit, decided per vocabulary shard as nvllm_step_sample does).
+ * The library keeps the (temperatures, seed, batch) it uploaded last and uploads again only when they differ.  Greedy and
+ * sampled fast steps and nvllm_step* calls may be mixed freely.  enqueue_sample is the pipelined form: its ids come out of
+ * nvllm_decode_collect; under tensor parallelism it is synchronous, like nvllm_decode_enqueue. */
+int nvllm_decode_next_sample(nvllm_model* m, const float* temperatures, uint64_t seed, uint32_t* next_ids);
+int nvllm_decode_enqueue_sample(nvllm_model* m, const float* temperatures, uint64_t seed);
+
 /* per-decode-step algorithmic HBM bytes of the LAST step on this rank:
  * weight_bytes + sum_seq ctx*kv_tok + n_seqs*kv_tok (+ 4*n_seqs*vocab when logits left the device) */
 int64_t nvllm_last_step_bytes(const nvllm_model* m);

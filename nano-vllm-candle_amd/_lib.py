@@ -72,6 +72,8 @@ _SIGS = {
     "nvllm_decode_next": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "nvllm_decode_enqueue": (C.c_int, [_vp]),
     "nvllm_decode_collect": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "nvllm_decode_next_sample": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint32)]),
+    "nvllm_decode_enqueue_sample": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint64]),
     "nvllm_last_step_bytes": (C.c_int64, [_vp]),
     "nvllm_debug_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "nvllm_debug_stamps": (C.c_int, [_vp, C.c_int]),
@@ -107,7 +109,8 @@ _SIGS = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _DEBUG_EXPORTS_ADDED_LATER = ("nvllm_debug_stamps", "nvllm_debug_stamps_read", "nvllm_ctx_create_null_comm", "nvllm_debug_set_option",
-                              "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter", "nvllm_model_set_attention_schedule")
+                              "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter", "nvllm_model_set_attention_schedule",
+                              "nvllm_decode_next_sample", "nvllm_decode_enqueue_sample")
 
 _lib = None
 

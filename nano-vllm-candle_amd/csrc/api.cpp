@@ -466,6 +466,18 @@ struct nvllm_model {
     float *ssqA = nullptr, *ssqB = nullptr;  // deferred-norm partial sums of squares [groups][kFusedMaxRows]
     uint64_t* d_keys = nullptr;              // device sampling: per-row RNG keys and temperatures
     float* d_temps = nullptr;
+    // sampled decode fast path (nvllm_decode_next_sample): what the sampling epilogue of the LM head reads.  The device copies of
+    // the temperatures and per-row base words are re-uploaded (through the pinned words of samp_pin) only when the host copy
+    // of the last upload -- temperatures, seed, batch -- differs from the call's
+    float *d_samp_temps = nullptr, *part_sval = nullptr;
+    uint64_t* d_samp_base = nullptr;
+    int* part_sidx = nullptr;
+    uint64_t* samp_pin = nullptr;  // pinned: [max_seqs] base words, then [max_seqs] temperatures
+    hipEvent_t samp_ev = nullptr;  // the last upload from samp_pin has been read
+    std::vector<float> samp_temps;
+    std::vector<int64_t> samp_ids;
+    uint64_t samp_seed = 0;
+    const float* step_temps = nullptr;  // non-null while a sampled fast step is being enqueued: the LM head draws
     // The streaming GEMM's in-launch split-K combine (epilogues 1-3) is OFF by default: measured slower than slabs + a
     // consumer launch on MI355X (Qwen3-8B batch 64: 8.6 vs 6.4 ms/step; 32B TP=8 shard: 8.9 vs 6.5 ms) -- one workgroup
     // per n-group reads every slab behind an agent-scope release of all the others.  nvllm_debug_set_option turns it on.
@@ -635,13 +647,17 @@ static void free_kv(nvllm_model* m) {
     m->kcache.clear(); m->vcache.clear(); m->vlocache.clear(); m->klocache.clear();
     void* ptrs[] = {m->d_block_tables, m->d_ids, m->d_pos, m->d_slot, m->d_tile_row0, m->d_tile_nrows, m->d_tile_slot,
                     m->d_last_rows, m->d_tile_order, m->d_tile_last, m->d_group_order, m->resid, m->slabs, m->qbuf, m->logits, m->d_maxval, m->red, m->xh, m->xl, m->xh2, m->xl2, m->ctxh, m->ctxl, m->ssqA, m->ssqB, m->d_next,
-                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps};
+                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps, m->d_samp_temps, m->d_samp_base, m->part_sval, m->part_sidx};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     m->d_block_tables = nullptr; m->d_ids = nullptr; m->d_pos = m->d_slot = m->d_tile_row0 = m->d_tile_nrows = m->d_tile_slot = m->d_last_rows = m->d_tile_order = m->d_tile_last = m->d_group_order = nullptr;
     m->resid = m->slabs = m->qbuf = m->logits = m->d_maxval = m->red = nullptr; m->xh = m->xl = m->xh2 = m->xl2 = m->ctxh = m->ctxl = nullptr; m->ssqA = m->ssqB = nullptr; m->d_next = nullptr; m->part_val = nullptr; m->part_idx = nullptr; m->argmax_scratch = nullptr; m->attn_po = m->attn_pml = nullptr;
     m->bal = AttnBalance();
     m->bal_on = false;
     m->tap_h = m->tap_res = nullptr; m->cosv = m->sinv = nullptr; m->tickets = nullptr; m->qkv_out = nullptr; m->d_keys = nullptr; m->d_temps = nullptr;
+    m->d_samp_temps = m->part_sval = nullptr; m->d_samp_base = nullptr; m->part_sidx = nullptr;
+    if (m->samp_pin) (void)hipHostFree(m->samp_pin);
+    m->samp_pin = nullptr;
+    m->samp_ids.clear();  // nothing uploaded
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     m->h_stage = nullptr;
     m->num_blocks = 0;
@@ -654,6 +670,7 @@ extern "C" int nvllm_model_destroy(nvllm_model* m) {
     free_kv(m);
     if (m->pin_ids) (void)hipHostFree(m->pin_ids);
     for (hipEvent_t e : m->pend_ev) if (e) (void)hipEventDestroy(e);
+    if (m->samp_ev) (void)hipEventDestroy(m->samp_ev);
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
     (void)hipFree(m->embed); (void)hipFree(m->lm_head.data); (void)hipFree(m->norm);
     for (auto& w : m->layers) {
@@ -980,8 +997,14 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
     // one partial per LM-head wave: at most V_l/16 n-tiles rounded up to whole workgroups (<= 8 waves each)
     if (!rc) rc = dmalloc(ctx, &m->part_val, (size_t)(m->V_l / 16 + 16) * max_seqs);
     if (!rc) rc = dmalloc(ctx, &m->part_idx, (size_t)(m->V_l / 16 + 16) * max_seqs);
-    if (!rc) rc = dmalloc(ctx, &m->argmax_scratch, (size_t)max_seqs + 1);
-    if (!rc) HIPCHK(ctx, hipMemsetAsync(m->argmax_scratch, 0, ((size_t)max_seqs + 1) * 8, ctx->stream));
+    if (!rc) rc = dmalloc(ctx, &m->part_sval, (size_t)(m->V_l / 16 + 16) * max_seqs);
+    if (!rc) rc = dmalloc(ctx, &m->part_sidx, (size_t)(m->V_l / 16 + 16) * max_seqs);
+    if (!rc) rc = dmalloc(ctx, &m->d_samp_temps, (size_t)max_seqs);
+    if (!rc) rc = dmalloc(ctx, &m->d_samp_base, (size_t)max_seqs);
+    if (!rc) rc = dmalloc(ctx, &m->argmax_scratch, sample_scratch_words(max_seqs));  // the sampled finish needs the larger one
+    if (!rc) HIPCHK(ctx, hipMemsetAsync(m->argmax_scratch, 0, sample_scratch_words(max_seqs) * 8, ctx->stream));
+    if (!rc) HIPCHK(ctx, hipHostMalloc((void**)&m->samp_pin, (size_t)max_seqs * 12, hipHostMallocDefault));
+    if (!rc && !m->samp_ev) HIPCHK(ctx, hipEventCreateWithFlags(&m->samp_ev, hipEventDisableTiming));
     if (rc) return rc;
     m->h_stage_bytes = (R * 24 + (size_t)max_seqs * 4) * sizeof(int) + 256;
     HIPCHK(ctx, hipHostMalloc(&m->h_stage, m->h_stage_bytes, hipHostMallocDefault));
@@ -1152,6 +1175,22 @@ static bool fused_plan(const nvllm_model* m, int R, FusedPlan& p) {
     return true;
 }
 
+// The LM head of a sampled fast step (nvllm_decode_next_sample): the draw happens in the GEMM's epilogue, the finish kernel
+// leaves per row what launch_sample_rows leaves -- (local id, plain max) for a degenerate row, else (local id, winning score).
+static int lm_head_sample(nvllm_model* m, const GemmPlan& pl, int n_last, const RowNorm* rn, uint32_t* ids_dst, float* val_dst) {
+    nvllm_ctx* ctx = m->ctx;
+    SampleArgs sa;
+    sa.temps = m->d_samp_temps; sa.base = m->d_samp_base; sa.pos = m->d_pos; sa.idx_offset = ctx->tp_rank * m->V_l;
+    sa.part_sval = m->part_sval; sa.part_sidx = m->part_sidx; sa.nan_flags = sample_nan_flags(m->argmax_scratch, n_last);
+    const int H = m->H, n_parts = gemm_argmax_parts(pl, m->V_l);
+    PROF(m, PROF_LMHEAD, launch_gemm_sample(pl, m->xh, m->xl, H, m->lm_head, n_last, m->part_val, m->part_idx, sa, rn, ctx->stream));
+    if (pl.lm_nt > 0)
+        HIPCHK(ctx, launch_sample_finish_rows(m->part_val, m->part_idx, sa, n_parts, n_last, ids_dst, val_dst, ctx->stream));
+    else
+        HIPCHK(ctx, launch_sample_finish_parts(m->part_val, m->part_idx, sa, n_parts, n_last, m->argmax_scratch, ids_dst, val_dst, ctx->stream));
+    return NVLLM_OK;
+}
+
 static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n_tiles, int qt, int n_last, int logits_row0) {
     nvllm_ctx* ctx = m->ctx;
     hipStream_t s = ctx->stream;
@@ -1313,10 +1352,11 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         GemmPlan pl = plan_lmhead(n_last, m->V_l, H);
         float* lg = m->want_logits ? m->logits + (size_t)logits_row0 * m->V_l : nullptr;
         rn.row_idx = m->d_last_rows;
-        PROF(m, PROF_LMHEAD, launch_gemm_argmax(pl, m->xh, m->xl, H, m->lm_head, lg, n_last, m->part_val, m->part_idx, &rn, s));
         const int tps = ctx->tp_size;  // vocab-parallel: every rank leaves (id, max) of its shard for the gather in finish_logits
         uint32_t* ids_dst = tps == 1 ? m->d_next + logits_row0 : m->d_next + m->cur_n + (size_t)ctx->tp_rank * m->cur_n + logits_row0;
         float* val_dst = tps == 1 ? nullptr : m->d_maxval + (size_t)ctx->tp_rank * m->cur_n + logits_row0;
+        if (m->step_temps) return lm_head_sample(m, pl, n_last, &rn, ids_dst, val_dst);
+        PROF(m, PROF_LMHEAD, launch_gemm_argmax(pl, m->xh, m->xl, H, m->lm_head, lg, n_last, m->part_val, m->part_idx, &rn, s));
         if (pl.lm_nt > 0)
             HIPCHK(ctx, launch_argmax_rows(m->part_val, m->part_idx, gemm_argmax_parts(pl, m->V_l), n_last, ids_dst, val_dst, s));
         else
@@ -1510,10 +1550,11 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         // logits are stored only when the caller asked for them; the greedy id always comes from the
         // GEMM epilogue's per-wave partial arg-max (LAST max wins), finished by one small kernel
         float* lg = m->want_logits ? m->logits + (size_t)logits_row0 * m->V_l : nullptr;
-        PROF(m, PROF_LMHEAD, launch_gemm_argmax(pl, m->xh, m->xl, H, m->lm_head, lg, n_last, m->part_val, m->part_idx, nullptr, s));
         const int tp = ctx->tp_size;
         uint32_t* ids_dst = tp == 1 ? m->d_next + logits_row0 : m->d_next + m->cur_n + (size_t)ctx->tp_rank * m->cur_n + logits_row0;
         float* val_dst = tp == 1 ? nullptr : m->d_maxval + (size_t)ctx->tp_rank * m->cur_n + logits_row0;
+        if (m->step_temps) return lm_head_sample(m, pl, n_last, nullptr, ids_dst, val_dst);
+        PROF(m, PROF_LMHEAD, launch_gemm_argmax(pl, m->xh, m->xl, H, m->lm_head, lg, n_last, m->part_val, m->part_idx, nullptr, s));
         if (pl.lm_nt > 0)
             HIPCHK(ctx, launch_argmax_rows(m->part_val, m->part_idx, gemm_argmax_parts(pl, m->V_l), n_last, ids_dst, val_dst, s));
         else
@@ -1822,8 +1863,32 @@ static int step_impl(nvllm_model* m, int n_seqs, const int64_t* seq_ids, const u
     return NVLLM_OK;
 }
 
-// enqueue one more decode step for the resident batch (no host sync): everything up to the device arg-max
-static int decode_core(nvllm_model* m) {
+// Sampling state of the resident batch for the LM head's sampling epilogue: temperatures and the per-row base words
+// finalize(seed * C + seq_id) (the inner half of sample_key; the kernel adds the position it has on the device).  A steady
+// decode loop repeats (temperatures, seed, batch), so the upload happens once; it goes through pinned words (a copy from
+// pageable memory would synchronise the stream), guarded by an event because those words are rewritten by the next change.
+static int upload_sampling(nvllm_model* m, int n, const float* temperatures, uint64_t seed) {
+    nvllm_ctx* ctx = m->ctx;
+    if (m->samp_seed == seed && m->samp_ids == m->last_ids && !memcmp(m->samp_temps.data(), temperatures, (size_t)n * 4)) return NVLLM_OK;
+    HIPCHK(ctx, hipEventSynchronize(m->samp_ev));
+    uint64_t* h_base = m->samp_pin;
+    float* h_temps = reinterpret_cast<float*>(m->samp_pin + m->max_seqs);
+    for (int i = 0; i < n; ++i) {
+        h_base[i] = synth_finalize(seed * 0x9E3779B97F4A7C15ULL + (uint64_t)m->last_ids[i]);
+        h_temps[i] = temperatures[i];
+    }
+    HIPCHK(ctx, hipMemcpyAsync(m->d_samp_base, h_base, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(m->d_samp_temps, h_temps, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(m->samp_ev, ctx->stream));
+    m->samp_ids = m->last_ids;
+    m->samp_temps.assign(temperatures, temperatures + n);
+    m->samp_seed = seed;
+    return NVLLM_OK;
+}
+
+// enqueue one more decode step for the resident batch (no host sync): everything up to the device arg-max, or -- with
+// temperatures -- up to the draw in the LM head's epilogue
+static int decode_core(nvllm_model* m, const float* temperatures = nullptr, uint64_t seed = 0) {
     nvllm_ctx* ctx = m->ctx;
     const int n = (int)m->last_ids.size();
     if (n == 0) return fail(ctx, NVLLM_ESTATE, "no previous step to continue");
@@ -1865,7 +1930,10 @@ static int decode_core(nvllm_model* m) {
     m->want_logits = false;
     m->cur_n = n;
     set_attn_split(m, n, *std::max_element(m->last_lens.begin(), m->last_lens.end()) + 1);
+    if (temperatures) { const int rcs = upload_sampling(m, n, temperatures, seed); if (rcs) return rcs; }
+    m->step_temps = temperatures;
     int rc = forward_chunk(m, n, n, 1, n, 0);
+    m->step_temps = nullptr;
     if (rc) return rc;
     int64_t kv_tokens = 0;
     for (int i = 0; i < n; ++i) {
@@ -1885,16 +1953,34 @@ extern "C" int nvllm_decode_next(nvllm_model* m, uint32_t* next_ids) {
     return finish_logits(m, (int)m->last_ids.size(), next_ids, nullptr);
 }
 
+extern "C" int nvllm_decode_next_sample(nvllm_model* m, const float* temperatures, uint64_t seed, uint32_t* next_ids) {
+    if (!m) return NVLLM_EINVAL;
+    if (!temperatures) return fail(m->ctx, NVLLM_EINVAL, "temperatures is NULL");
+    if (!m->pending.empty()) return fail(m->ctx, NVLLM_ESTATE, "collect the enqueued decode steps first");
+    int rc = decode_core(m, temperatures, seed);
+    if (rc) return rc;
+    return finish_logits(m, (int)m->last_ids.size(), next_ids, nullptr);
+}
+
 // Pipelined form: enqueue returns as soon as the step is on the stream (its ids travel to a pinned slot behind
 // an event); collect waits for the OLDEST enqueued step.  Keeping one step in flight hides the host round trip
 // (the reference's engine consumes ids once per step, llm_engine.rs:239-242; asynchronous scheduling sees them one
 // step late).  Tensor-parallel contexts fall back to a synchronous step inside enqueue.
+static int decode_enqueue_impl(nvllm_model* m, const float* temperatures, uint64_t seed);
 extern "C" int nvllm_decode_enqueue(nvllm_model* m) {
     if (!m) return NVLLM_EINVAL;
+    return decode_enqueue_impl(m, nullptr, 0);
+}
+extern "C" int nvllm_decode_enqueue_sample(nvllm_model* m, const float* temperatures, uint64_t seed) {
+    if (!m) return NVLLM_EINVAL;
+    if (!temperatures) return fail(m->ctx, NVLLM_EINVAL, "temperatures is NULL");
+    return decode_enqueue_impl(m, temperatures, seed);
+}
+static int decode_enqueue_impl(nvllm_model* m, const float* temperatures, uint64_t seed) {
     nvllm_ctx* ctx = m->ctx;
     const int n = (int)m->last_ids.size();
     if ((int)m->pending.size() >= kMaxPending) return fail(ctx, NVLLM_ESTATE, "too many decode steps in flight (max %d)", kMaxPending);
-    int rc = decode_core(m);
+    int rc = decode_core(m, temperatures, seed);
     if (rc) return rc;
     if (!m->pin_ids) {
         HIPCHK(ctx, hipHostMalloc((void**)&m->pin_ids, (size_t)kMaxPending * m->max_seqs * 4, hipHostMallocDefault));

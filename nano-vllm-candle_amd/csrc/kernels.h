@@ -127,6 +127,35 @@ hipError_t launch_argmax_rows(const float* part_val, const int* part_idx, int n_
 hipError_t launch_argmax_parts(const float* part_val, const int* part_idx, int n_parts, int M, void* scratch,
                                uint32_t* ids, float* maxval, hipStream_t s);
 
+// ---- sampled LM head: the draw of launch_sample_rows (same scores, bit for bit) in the LM-head epilogue, logits never stored.
+// Decode steps only: output row r is row r of the step (pos[r] = position of the token fed to it).  Each wave reduces, beside
+// the plain partial arg-max (NaN ranks below every number), the partial arg-max of v / t - log(-log(u)) with
+// t = max(temps[r], 1e-6), u = sample_u01(key_r, idx_offset + i), key_r = finalize(base[r] + (pos[r] + 1) * 0xD1B54A32D192ED03)
+// (== api.cpp sample_key with base[r] = finalize(seed * 0x9E3779B97F4A7C15 + seq_id)), and raises nan_flags[r] when it meets a
+// NaN.  The finish emits the plain winner for a degenerate row (NaN seen, or plain max not finite: exactly the rows whose
+// softmax weights do not sum to a positive finite number), else the perturbed one; value word = plain max / winning score.
+struct SampleArgs {
+    const float* temps = nullptr;     // [M]
+    const uint64_t* base = nullptr;   // [M]
+    const int* pos = nullptr;         // [M]
+    int idx_offset = 0;               // first global vocabulary id of this shard
+    float* part_sval = nullptr;       // perturbed partials, laid out like part_val / part_idx
+    int* part_sidx = nullptr;
+    unsigned* nan_flags = nullptr;    // [M], zero between steps (the finish kernels re-arm them)
+};
+// scratch of the sampled finish kernels: sample_scratch_words(M) 64-bit words, zero before the first use and left zero again:
+// [0] ticket, [1, M] plain keys, [M+1, 2M] perturbed keys, then M 32-bit NaN flags (sample_nan_flags)
+inline size_t sample_scratch_words(int M) { return (size_t)1 + 2 * (size_t)M + ((size_t)M + 1) / 2; }
+inline unsigned* sample_nan_flags(void* scratch, int M) { return reinterpret_cast<unsigned*>(reinterpret_cast<unsigned long long*>(scratch) + 1 + 2 * (size_t)M); }
+// launch_gemm_argmax with the sampling epilogue (the same plans, the same partial counts); sa.nan_flags = sample_nan_flags(scratch, M)
+hipError_t launch_gemm_sample(const GemmPlan& p, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w, int M,
+                              float* part_val, int* part_idx, const SampleArgs& sa, const RowNorm* rn, hipStream_t s);
+// finish of the streaming kernel (partials [row][n_parts]) and of the chunked one ([n_parts][row], ticketed)
+hipError_t launch_sample_finish_rows(const float* part_val, const int* part_idx, const SampleArgs& sa, int n_parts, int M, uint32_t* ids,
+                                     float* val, hipStream_t s);
+hipError_t launch_sample_finish_parts(const float* part_val, const int* part_idx, const SampleArgs& sa, int n_parts, int M, void* scratch,
+                                      uint32_t* ids, float* val, hipStream_t s);
+
 // ---- (embed +) add + RMSNorm ----------------------------------------------------------------------
 struct NormArgs {
     const float* in = nullptr;        // [n_slabs][rows_in][H] f32 (slab sum) ; or nullptr with ids/embed

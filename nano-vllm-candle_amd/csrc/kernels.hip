@@ -185,11 +185,65 @@ hipError_t launch_split_hilo(const float* x, bf16_bits* hi, bf16_bits* lo, int64
 // MODE 0: f32 slabs.  MODE 1: + per-wave partial arg-max (LM head).  MODE 2: SwiGLU epilogue -- the weight is
 // the gate/up matrix interleaved in 16-row tiles (NT == 2: tile 0 = gate, tile 1 = up of the same 16 features),
 // the wave writes silu(gate)*up as bf16 hi/lo planes act[M][N/2] (SiluAndMul, activation.rs:13-18); no split-K.
+// MODE 3: MODE 1 with the sampling epilogue (SampleArgs, kernels.h; `out` unused).  The other modes take an empty struct in
+// its place and compile as before.
+//
+// The sampling epilogue, shared with the streaming LM head.  A lane owns one row of each row block; after the main loop
+// (the weight registers are dead) it loads the row's temperature and derives the row's RNG key, then walks its
+// accumulators once, keeping two running arg-maxes: the plain one and the one of the Gumbel-perturbed scores.  The counter
+// of element i is key + (i + 1) * GOLDEN; the elements of a lane are at compile-time distances, so the 64-bit product
+// is formed once per row (SampleRow::k0) and every element adds a constant.  Scores are the expression of
+// sample_rows_kernel, bit for bit; a NaN logit or score ranks below every number, ties go to the higher index.
+__host__ __device__ inline float sample_u01(uint64_t key, uint32_t i);
+constexpr uint64_t kSampleGolden = 0x9E3779B97F4A7C15ULL;
+struct SampleRow {
+    float t;
+    uint64_t k0;  // counter of the lane's element 0: key + (global id + 1) * kSampleGolden
+};
+__device__ __forceinline__ SampleRow sample_row(const SampleArgs& sa, int row, int idx0) {
+    SampleRow r;
+    r.t = fmaxf(sa.temps[row], 1e-6f);
+    const uint64_t key = synth_finalize(sa.base[row] + (uint64_t)(sa.pos[row] + 1) * 0xD1B54A32D192ED03ULL);
+    r.k0 = key + ((uint64_t)(uint32_t)(idx0 + sa.idx_offset) + 1) * kSampleGolden;
+    return r;
+}
+struct SamplePart {
+    float pv = -INFINITY, sv = -INFINITY;  // plain / perturbed running max
+    int pi = -1, si = -1;                  // their local vocabulary ids (-1: nothing seen)
+    bool nan = false;
+};
+__device__ __forceinline__ bool sample_better(float v, int i, float bv, int bi) { return bi < 0 || v > bv || (v == bv && i > bi); }
+// element `idx` (local id) at distance `delta` from the lane's element 0
+__device__ __forceinline__ void sample_take(SamplePart& p, float v, int idx, int delta, const SampleRow& r) {
+    if (v != v) { p.nan = true; v = -INFINITY; }
+    if (sample_better(v, idx, p.pv, p.pi)) { p.pv = v; p.pi = idx; }
+    const uint64_t x = synth_finalize(r.k0 + (uint64_t)delta * kSampleGolden);
+    const float u = ((float)(x >> 40) + 0.5f) * 5.9604644775390625e-08f;  // == sample_u01(key, global id)
+    float sc = v / r.t - logf(-logf(u));
+    if (sc != sc) sc = -INFINITY;
+    if (sample_better(sc, idx, p.sv, p.si)) { p.sv = sc; p.si = idx; }
+}
+// the four lanes that share a row (lane, lane ^ 16, lane ^ 32, lane ^ 48) meet; a NaN raises the row's flag directly
+__device__ __forceinline__ void sample_merge_row(SamplePart& p, bool row_ok, unsigned* flag) {
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+        const float ov = __shfl_xor(p.pv, o), osv = __shfl_xor(p.sv, o);
+        const int oi = __shfl_xor(p.pi, o), osi = __shfl_xor(p.si, o);
+        if (oi >= 0 && sample_better(ov, oi, p.pv, p.pi)) { p.pv = ov; p.pi = oi; }
+        if (osi >= 0 && sample_better(osv, osi, p.sv, p.si)) { p.sv = osv; p.si = osi; }
+    }
+    if (p.nan && row_ok) atomicOr(flag, 1u);
+}
+
+struct NoSample {};
+template <bool SAMPLE> using SampleParam = std::conditional_t<SAMPLE, SampleArgs, NoSample>;
+
 template <int MT, int NT, int NW, int KC, int MODE>
 __global__ void __launch_bounds__(NW * 64)
 gemm_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl, int ldx, const uint4* __restrict__ wp,
             float* __restrict__ out, int M, int N, int KT, int kt_per_split, float* __restrict__ part_val,
-            int* __restrict__ part_idx, uint16_t* __restrict__ act_hi, uint16_t* __restrict__ act_lo, RowNorm rn) {
+            int* __restrict__ part_idx, uint16_t* __restrict__ act_hi, uint16_t* __restrict__ act_lo, RowNorm rn,
+            SampleParam<MODE == 3> sa) {
     // LDS: two buffers of [2 planes][MT][KC][64 lanes] 16-byte slots, filled by LDS-DMA (global_load_lds):
     // the image is lane-linear per fragment, so every wave-DMA writes one contiguous 1 KiB and every
     // ds_read_b128 of a fragment is conflict-free.
@@ -293,7 +347,7 @@ gemm_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl, in
             compute(1, wf1);
         }
     }
-    if constexpr (MODE == 1) {  // LM head on a deferred final norm: logits = rinv[row] * acc
+    if constexpr (MODE == 1 || MODE == 3) {  // LM head on a deferred final norm: logits = rinv[row] * acc
         if (rn.ssq) {
 #pragma unroll
             for (int b = 0; b < MT; ++b) {
@@ -377,6 +431,31 @@ gemm_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl, in
             }
         }
     }
+    if constexpr (MODE == 3) {
+        // sampled LM head: both partial arg-maxes of the wave's NT*16 features, part_*[wave_global][row]; finished by
+        // sample_finish_parts_kernel
+        const int wg = blockIdx.x * NW + wave;
+#pragma unroll
+        for (int b = 0; b < MT; ++b) {
+            if (m0 + b * 16 >= M) continue;  // a row block past the last row (uniform)
+            const int row = m0 + b * 16 + l15;
+            const SampleRow sr = sample_row(sa, min(row, M - 1), nt0 * 16 + grp * 4);
+            SamplePart p;
+#pragma unroll
+            for (int a = 0; a < NT; ++a) {
+                if (nt0 + a >= ntiles) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sample_take(p, acc[a][b][r], (nt0 + a) * 16 + grp * 4 + r, a * 16 + r, sr);
+            }
+            sample_merge_row(p, row < M, sa.nan_flags + min(row, M - 1));
+            if (grp == 0 && row < M) {
+                part_val[(size_t)wg * M + row] = p.pv;
+                part_idx[(size_t)wg * M + row] = p.pi;
+                sa.part_sval[(size_t)wg * M + row] = p.sv;
+                sa.part_sidx[(size_t)wg * M + row] = p.si;
+            }
+        }
+    }
 }
 
 // finish the fused LM-head arg-max.  part_*[p][row] (row fastest): thread = (row%64, plane); a block scans one
@@ -433,6 +512,71 @@ __global__ void __launch_bounds__(256) argmax_parts_kernel(const float* __restri
         if (threadIdx.x == 0) *ticket = 0;
     }
 }
+__device__ __forceinline__ float argmax_key_value(unsigned long long k) {
+    unsigned u = (unsigned)(k >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __builtin_bit_cast(float, u);
+}
+// what a sampled row emits from its merged keys: the plain winner when the row is degenerate (a NaN was seen, or the
+// plain max is not finite), else the perturbed one; the value word is the plain max / the winning score
+__device__ __forceinline__ void sample_emit(unsigned long long pk, unsigned long long sk, unsigned nan, uint32_t* id, float* val) {
+    const float pmax = argmax_key_value(pk);
+    const bool degenerate = nan != 0 || !(fabsf(pmax) < INFINITY);
+    const unsigned long long k = degenerate ? pk : sk;
+    *id = (uint32_t)(k & 0xffffffffu);
+    if (val) *val = argmax_key_value(k);
+}
+// the sampled twin of argmax_parts_kernel: two keys per row (plain, perturbed) and the row's NaN flag; the last block
+// decides per row and re-arms ticket, keys and flags
+__global__ void __launch_bounds__(256) sample_finish_parts_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
+                                                                  const float* __restrict__ part_sval, const int* __restrict__ part_sidx,
+                                                                  int n_parts, int M, unsigned long long* __restrict__ keys,
+                                                                  unsigned long long* __restrict__ skeys, unsigned* __restrict__ nan_flags,
+                                                                  unsigned* __restrict__ ticket, uint32_t* __restrict__ ids,
+                                                                  float* __restrict__ val) {
+    __shared__ unsigned long long sk[2][256];
+    __shared__ unsigned last;
+    const int r = threadIdx.x & 63, plane = threadIdx.x >> 6;
+    const int row = blockIdx.y * 64 + r;
+    const int per = (n_parts + gridDim.x - 1) / gridDim.x;
+    const int p0 = blockIdx.x * per, p1 = min(n_parts, p0 + per);
+    unsigned long long best = 0, sbest = 0;
+    if (row < M)
+        for (int p = p0 + plane; p < p1; p += 4) {
+            const int i = part_idx[(size_t)p * M + row], si = part_sidx[(size_t)p * M + row];
+            if (i >= 0) {  // an idle wave leaves -1 in both
+                const unsigned long long k = argmax_key(part_val[(size_t)p * M + row], i);
+                const unsigned long long s = argmax_key(part_sval[(size_t)p * M + row], si);
+                best = k > best ? k : best;
+                sbest = s > sbest ? s : sbest;
+            }
+        }
+    sk[0][threadIdx.x] = best;
+    sk[1][threadIdx.x] = sbest;
+    __syncthreads();
+    if (plane == 0 && row < M) {
+        for (int q = 1; q < 4; ++q) {
+            best = sk[0][q * 64 + r] > best ? sk[0][q * 64 + r] : best;
+            sbest = sk[1][q * 64 + r] > sbest ? sk[1][q * 64 + r] : sbest;
+        }
+        if (best) { atomicMax(&keys[row], best); atomicMax(&skeys[row], sbest); }
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x * gridDim.y - 1 ? 1u : 0u;
+    __syncthreads();
+    if (last) {
+        __threadfence();
+        for (int i = threadIdx.x; i < M; i += blockDim.x) {
+            const unsigned long long k = __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long s = __hip_atomic_load(&skeys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned f = __hip_atomic_load(&nan_flags[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sample_emit(k, s, f, ids + i, val ? val + i : nullptr);
+            keys[i] = 0; skeys[i] = 0; nan_flags[i] = 0;
+        }
+        if (threadIdx.x == 0) *ticket = 0;
+    }
+}
 
 // every split covers a whole number of KC-chunks
 void set_split(GemmPlan& p, int KT, int want) {
@@ -467,6 +611,7 @@ struct GemmExtra {
     bf16_bits* act_hi = nullptr; // MODE 2
     bf16_bits* act_lo = nullptr;
     RowNorm rn;
+    SampleArgs sa;               // MODE 3
 };
 
 template <int MT, int NT, int NW, int KC, int MODE>
@@ -477,8 +622,10 @@ static hipError_t gemm_launch_t(const GemmPlan& p, const bf16_bits* xh, const bf
     const size_t lds = (size_t)2 * 2 * MT * KC * 1024 + (size_t)4 * MT * 16 * 4;
     static std::atomic<uint64_t> lds_set{0};
     ensure_dyn_lds(reinterpret_cast<const void*>(gemm_kernel<MT, NT, NW, KC, MODE>), lds, lds_set);
+    SampleParam<MODE == 3> sa;
+    if constexpr (MODE == 3) sa = x.sa;
     gemm_kernel<MT, NT, NW, KC, MODE><<<grid, NW * 64, lds, s>>>(xh, xl, ldx, w.data, out, M, w.N, w.K / 32, p.kt_per_split,
-                                                                x.part_val, x.part_idx, x.act_hi, x.act_lo, x.rn);
+                                                                x.part_val, x.part_idx, x.act_hi, x.act_lo, x.rn, sa);
     return hipGetLastError();
 }
 
@@ -508,10 +655,14 @@ template <int MODE>
 static hipError_t gemm_dispatch(const GemmPlan& p, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w,
                                 float* out, int M, const GemmExtra& x, hipStream_t s) {
     if ((w.K / 32) % p.kc != 0 || p.kt_per_split % p.kc != 0) return hipErrorInvalidValue;
-    if (p.nw == 2) return gemm_dispatch_nw<2, MODE>(p, xh, xl, ldx, w, out, M, x, s);
-    if (p.nw == 4) return gemm_dispatch_nw<4, MODE>(p, xh, xl, ldx, w, out, M, x, s);
-    if (p.nw == 8) return gemm_dispatch_nw<8, MODE>(p, xh, xl, ldx, w, out, M, x, s);
-    return hipErrorInvalidValue;
+    if constexpr (MODE == 3) {  // plan_lmhead's plans only: four waves
+        return p.nw == 4 ? gemm_dispatch_nw<4, MODE>(p, xh, xl, ldx, w, out, M, x, s) : hipErrorInvalidValue;
+    } else {
+        if (p.nw == 2) return gemm_dispatch_nw<2, MODE>(p, xh, xl, ldx, w, out, M, x, s);
+        if (p.nw == 4) return gemm_dispatch_nw<4, MODE>(p, xh, xl, ldx, w, out, M, x, s);
+        if (p.nw == 8) return gemm_dispatch_nw<8, MODE>(p, xh, xl, ldx, w, out, M, x, s);
+        return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_gemm(const GemmPlan& p, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w,
@@ -526,10 +677,16 @@ hipError_t launch_gemm(const GemmPlan& p, const bf16_bits* xh, const bf16_bits* 
 // owns NT n-tiles for the WHOLE K and keeps two 2-k-tile weight sets (2*NT KiB each) in flight while all 64 rows
 // of x ride through LDS in 8-k-tile chunks (double buffered, every wave stages one k-tile of a chunk).
 // ---------------------------------------------------------------------------------------------------
+// NCH >= kLmSample: the sampling epilogue instead of the greedy one (SampleArgs, kernels.h; `out` unused), NCH - kLmSample
+// chunks unrolled.  By then the two weight sets are dead, so the row's temperature and counter and the second running
+// arg-max live in their registers.  The greedy instantiations take an empty struct in its place and compile as before.
+constexpr int kLmSample = 16;
 template <int MT, int NT, int NCH>
 __global__ void __launch_bounds__(512) lmhead_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl, int ldx,
                                                      const uint4* __restrict__ wp, float* __restrict__ out, int M, int N, int KT,
-                                                     float* __restrict__ part_val, int* __restrict__ part_idx, RowNorm rn) {
+                                                     float* __restrict__ part_val, int* __restrict__ part_idx, RowNorm rn,
+                                                     SampleParam<(NCH >= kLmSample)> sa) {
+    constexpr bool SAMPLE = NCH >= kLmSample;
     constexpr int NW = 8, KC = 8, SC = MT == 4 ? 1 : 2;  // 64 rows: 80 accumulator registers leave room for 1-k-tile sets only
     constexpr int FRAGS = 2 * MT * KC;  // 1 KiB fragments per x chunk: [2 planes][MT][KC]
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -593,7 +750,7 @@ __global__ void __launch_bounds__(512) lmhead_kernel(const uint16_t* __restrict_
     };
     // NCH > 0: the chunk loop is fully unrolled (the compiler then tracks every load in flight exactly; with a
     // back-edge it falls back to vmcnt(0) after each refill)
-    const int nchunks = NCH > 0 ? NCH : KT / KC;
+    const int nchunks = NCH % kLmSample > 0 ? NCH % kLmSample : KT / KC;
     stage(0, 0);
     issue_w(0, wA);
     issue_w(SC, wB);
@@ -642,6 +799,30 @@ __global__ void __launch_bounds__(512) lmhead_kernel(const uint16_t* __restrict_
         }
     }
     const int wg = (int)blockIdx.x * NW + wave;
+    if constexpr (SAMPLE) {
+        const size_t n_parts = (size_t)gridDim.x * NW;
+#pragma unroll
+        for (int b = 0; b < MT; ++b) {
+            if (b * 16 >= M) continue;  // a row block past the last row (uniform)
+            const int row = b * 16 + l15;
+            const SampleRow sr = sample_row(sa, min(row, M - 1), nt0 * 16 + grp * 4);
+            SamplePart p;
+#pragma unroll
+            for (int a = 0; a < NT; ++a) {
+                if (nt0 + a >= ntiles) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sample_take(p, acc[a][b][r], (nt0 + a) * 16 + grp * 4 + r, a * 16 + r, sr);
+            }
+            sample_merge_row(p, row < M, sa.nan_flags + min(row, M - 1));
+            if (grp == 0 && row < M) {  // part_*[row][wave]: one workgroup per row finishes (sample_finish_rows_kernel)
+                part_val[(size_t)row * n_parts + wg] = p.pv;
+                part_idx[(size_t)row * n_parts + wg] = p.pi;
+                sa.part_sval[(size_t)row * n_parts + wg] = p.sv;
+                sa.part_sidx[(size_t)row * n_parts + wg] = p.si;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < MT; ++b) {
         const int row = b * 16 + l15;
@@ -717,6 +898,54 @@ hipError_t launch_argmax_rows(const float* part_val, const int* part_idx, int n_
     argmax_rows_kernel<<<M, 256, 0, s>>>(part_val, part_idx, n_parts, ids, maxval);
     return hipGetLastError();
 }
+// the sampled twin: merges the plain and the perturbed partials of one row, decides (sample_emit), re-arms the row's flag
+__global__ void __launch_bounds__(256) sample_finish_rows_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
+                                                                 const float* __restrict__ part_sval, const int* __restrict__ part_sidx,
+                                                                 int n_parts, unsigned* __restrict__ nan_flags, uint32_t* __restrict__ ids,
+                                                                 float* __restrict__ val) {
+    __shared__ unsigned long long sk[2][4];
+    const int row = blockIdx.x;
+    const size_t r0 = (size_t)row * n_parts;
+    unsigned long long best = 0, sbest = 0;
+    for (int p0 = 0; p0 < n_parts; p0 += 256 * 2) {
+        int i2[2], si2[2]; float v2[2], sv2[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {  // unconditional loads (clamped), validity applied afterwards
+            const int p = min(p0 + u * 256 + (int)threadIdx.x, n_parts - 1);
+            i2[u] = part_idx[r0 + p]; v2[u] = part_val[r0 + p]; si2[u] = part_sidx[r0 + p]; sv2[u] = part_sval[r0 + p];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool ok = (p0 + u * 256 + (int)threadIdx.x) < n_parts && i2[u] >= 0;  // an idle wave leaves -1 in both
+            const unsigned long long k = ok ? argmax_key(v2[u], i2[u]) : 0ull, s = ok ? argmax_key(sv2[u], si2[u]) : 0ull;
+            best = k > best ? k : best;
+            sbest = s > sbest ? s : sbest;
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long k = ((unsigned long long)__shfl_xor((unsigned)(best >> 32), o) << 32) | __shfl_xor((unsigned)best, o);
+        const unsigned long long s = ((unsigned long long)__shfl_xor((unsigned)(sbest >> 32), o) << 32) | __shfl_xor((unsigned)sbest, o);
+        best = k > best ? k : best;
+        sbest = s > sbest ? s : sbest;
+    }
+    if ((threadIdx.x & 63) == 0) { sk[0][threadIdx.x >> 6] = best; sk[1][threadIdx.x >> 6] = sbest; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q) {
+            best = sk[0][q] > best ? sk[0][q] : best;
+            sbest = sk[1][q] > sbest ? sk[1][q] : sbest;
+        }
+        sample_emit(best, sbest, nan_flags[row], ids + row, val ? val + row : nullptr);
+        nan_flags[row] = 0;
+    }
+}
+hipError_t launch_sample_finish_rows(const float* part_val, const int* part_idx, const SampleArgs& sa, int n_parts, int M, uint32_t* ids,
+                                     float* val, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    sample_finish_rows_kernel<<<M, 256, 0, s>>>(part_val, part_idx, sa.part_sval, sa.part_sidx, n_parts, sa.nan_flags, ids, val);
+    return hipGetLastError();
+}
 
 template <int MT, int NT, int NCH>
 static hipError_t lmhead_launch_t(const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w, float* out, int M,
@@ -725,7 +954,7 @@ static hipError_t lmhead_launch_t(const bf16_bits* xh, const bf16_bits* xl, int 
     static std::atomic<uint64_t> lds_set{0};
     ensure_dyn_lds(reinterpret_cast<const void*>(lmhead_kernel<MT, NT, NCH>), lds, lds_set);
     const int waves = (w.N / 16 + NT - 1) / NT;
-    lmhead_kernel<MT, NT, NCH><<<(waves + 7) / 8, 512, lds, s>>>(xh, xl, ldx, w.data, out, M, w.N, w.K / 32, part_val, part_idx, rn);
+    lmhead_kernel<MT, NT, NCH><<<(waves + 7) / 8, 512, lds, s>>>(xh, xl, ldx, w.data, out, M, w.N, w.K / 32, part_val, part_idx, rn, NoSample{});
     return hipGetLastError();
 }
 
@@ -760,6 +989,40 @@ hipError_t launch_gemm_argmax(const GemmPlan& p, const bf16_bits* xh, const bf16
         return hipErrorNotSupported;
     }
     return gemm_dispatch<1>(p, xh, xl, ldx, w, out, M, x, s);
+}
+
+template <int MT, int NT, int NCH>
+static hipError_t lmhead_sample_launch_t(const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w, int M, float* part_val,
+                                         int* part_idx, const RowNorm& rn, const SampleArgs& sa, hipStream_t s) {
+    const size_t lds = (size_t)2 * (2 * MT * 8) * 1024 + (size_t)4 * MT * 16 * 4;
+    static std::atomic<uint64_t> lds_set{0};
+    ensure_dyn_lds(reinterpret_cast<const void*>(lmhead_kernel<MT, NT, NCH + kLmSample>), lds, lds_set);
+    const int waves = (w.N / 16 + NT - 1) / NT;
+    lmhead_kernel<MT, NT, NCH + kLmSample><<<(waves + 7) / 8, 512, lds, s>>>(xh, xl, ldx, w.data, nullptr, M, w.N, w.K / 32, part_val, part_idx,
+                                                                            rn, sa);
+    return hipGetLastError();
+}
+hipError_t launch_gemm_sample(const GemmPlan& p, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW& w, int M,
+                              float* part_val, int* part_idx, const SampleArgs& sa, const RowNorm* rn, hipStream_t s) {
+    if (!part_val || !part_idx || !sa.part_sval || !sa.part_sidx || !sa.temps || !sa.base || !sa.pos || !sa.nan_flags || p.n_split != 1)
+        return hipErrorInvalidValue;
+    GemmExtra x;
+    x.part_val = part_val; x.part_idx = part_idx; x.sa = sa;
+    if (rn) x.rn = *rn;
+    if (p.lm_nt > 0) {
+        if (M < 1 || M > 64 || w.K % 256) return hipErrorInvalidValue;
+        const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+#define NVLLM_LM(MT_, NT_)                                                                                        \
+    if (mt == MT_ && p.lm_nt == NT_)                                                                            \
+        return w.K == 1024 ? lmhead_sample_launch_t<MT_, NT_, 4>(xh, xl, ldx, w, M, part_val, part_idx, x.rn, sa, s) \
+                           : lmhead_sample_launch_t<MT_, NT_, 0>(xh, xl, ldx, w, M, part_val, part_idx, x.rn, sa, s);
+#define NVLLM_LM_MT(MT_) NVLLM_LM(MT_, 1) NVLLM_LM(MT_, 2) NVLLM_LM(MT_, 3) NVLLM_LM(MT_, 4) NVLLM_LM(MT_, 5) NVLLM_LM(MT_, 6)
+        NVLLM_LM_MT(1) NVLLM_LM_MT(2) NVLLM_LM_MT(4)
+#undef NVLLM_LM_MT
+#undef NVLLM_LM
+        return hipErrorNotSupported;
+    }
+    return gemm_dispatch<3>(p, xh, xl, ldx, w, nullptr, M, x, s);
 }
 
 // gate/up GEMM with the SwiGLU epilogue; w = interleaved gate_up [2I][K]; act planes [M][I]
@@ -800,6 +1063,17 @@ hipError_t launch_argmax_parts(const float* part_val, const int* part_idx, int n
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(scratch) + 1;
     dim3 grid(std::max(1, std::min(64, n_parts / 64)), (M + 63) / 64);
     argmax_parts_kernel<<<grid, 256, 0, s>>>(part_val, part_idx, n_parts, M, keys, ticket, ids, maxval);
+    return hipGetLastError();
+}
+hipError_t launch_sample_finish_parts(const float* part_val, const int* part_idx, const SampleArgs& sa, int n_parts, int M, void* scratch,
+                                      uint32_t* ids, float* val, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    if (sa.nan_flags != sample_nan_flags(scratch, M)) return hipErrorInvalidValue;  // the layout sample_scratch_words describes
+    unsigned* ticket = reinterpret_cast<unsigned*>(scratch);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(scratch) + 1;
+    dim3 grid(std::max(1, std::min(64, n_parts / 64)), (M + 63) / 64);
+    sample_finish_parts_kernel<<<grid, 256, 0, s>>>(part_val, part_idx, sa.part_sval, sa.part_sidx, n_parts, M, keys, keys + M, sa.nan_flags,
+                                                    ticket, ids, val);
     return hipGetLastError();
 }
 

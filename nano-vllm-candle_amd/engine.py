@@ -231,10 +231,14 @@ class Qwen3ModelRunner(ModelRunner):
                     categorical draw (llm_engine.rs:97-133) -- on the DEVICE (nvllm_step_sample), seeded per runner
                     (`seed`; the reference's RNG is unseeded, so a run of the reference is one such seed).
     greedy=True  -> ids come from the device arg-max (the reference's `argmax` fallback rule: last max).
+    fast_decode=True (with greedy=False): a decode call whose sequences are the previous call's, in the same order, each longer
+                    by exactly the id that call returned, draws through nvllm_decode_next_sample -- the same ids, no token
+                    lists uploaded, no logits stored; any other call goes through nvllm_step_sample.  The runner must be the
+                    only caller of its model between two calls.
     An empty sequence is fed as [eos] (the reference pads rows with eos and reads row 0, llm_engine.rs:80-90,181).
     Errors never propagate: any failure -> eos for every sequence (llm_engine.rs:153-175)."""
 
-    def __init__(self, model, greedy=False, seed=None, raise_errors=False):
+    def __init__(self, model, greedy=False, seed=None, raise_errors=False, fast_decode=False):
         self.model = model
         self.cfg = model.cfg
         self.eos_id = model.cfg.eos_token_id
@@ -242,6 +246,8 @@ class Qwen3ModelRunner(ModelRunner):
         self.seed = int.from_bytes(__import__("os").urandom(8), "little") if seed is None else int(seed)
         self.raise_errors = raise_errors
         self.last_error = None
+        self.fast_decode = fast_decode
+        self._resident = None  # (seq ids, token counts, last ids) the next call must show to continue on the device
 
     def run(self, seqs, is_prefill):
         if not seqs:
@@ -251,8 +257,15 @@ class Qwen3ModelRunner(ModelRunner):
             if self.greedy:
                 ids, _ = self.model.step([s.seq_id for s in seqs], toks, is_prefill)
             else:
-                ids, _ = self.model.step_sample([s.seq_id for s in seqs], toks, is_prefill, [s.temperature for s in seqs], self.seed)
+                sids, temps = [s.seq_id for s in seqs], [s.temperature for s in seqs]
+                now = (sids, [len(t) for t in toks], [t[-1] for t in toks])
+                if self.fast_decode and not is_prefill and now == self._resident:
+                    ids = self.model.decode_next_sample(temps, self.seed)[:len(seqs)]
+                else:
+                    ids, _ = self.model.step_sample(sids, toks, is_prefill, temps, self.seed)
+                self._resident = (sids, [len(t) + 1 for t in toks], [int(t) for t in ids])
         except Exception as e:  # noqa: BLE001 -- the reference logs and returns eos for all
+            self._resident = None
             if self.raise_errors:
                 raise
             self.last_error = e

@@ -289,6 +289,31 @@ class Qwen3ForCausalLM:
         _lib.check(_lib.lib().nvllm_decode_collect(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx.h)
         return buf
 
+    def _temps(self, temperatures):
+        temps = np.ascontiguousarray(temperatures, np.float32)
+        room = max(getattr(self, "max_seqs", 0), 1)
+        if temps.ndim != 1 or temps.size > room:
+            raise ValueError("one temperature per sequence of the previous step")
+        full = np.zeros(room, np.float32)  # the library reads one per sequence of ITS batch: never past the buffer
+        full[:temps.size] = temps
+        return full
+
+    def decode_next_sample(self, temperatures, seed, want_ids=True):
+        """decode_next with sample_token in the LM head's epilogue (nvllm_decode_next_sample): the ids step_sample would draw for
+        the same seed, temperatures (one per sequence of the previous step) and token lists; no logits stored, ids fed back on
+        the device"""
+        temps = self._temps(temperatures)
+        buf = np.empty(max(getattr(self, "max_seqs", 0), 1), np.uint32)
+        _lib.check(_lib.lib().nvllm_decode_next_sample(self.h, temps.ctypes.data_as(C.POINTER(C.c_float)), int(seed) & (2**64 - 1),
+                                                       buf.ctypes.data_as(C.POINTER(C.c_uint32)) if want_ids else None), self.ctx.h)
+        return buf
+
+    def decode_enqueue_sample(self, temperatures, seed):
+        """pipelined form of decode_next_sample: the ids come out of decode_collect"""
+        temps = self._temps(temperatures)
+        _lib.check(_lib.lib().nvllm_decode_enqueue_sample(self.h, temps.ctypes.data_as(C.POINTER(C.c_float)), int(seed) & (2**64 - 1)),
+                   self.ctx.h)
+
     PROF_KINDS = {"attn": 1, "gemm": 2, "norm": 3, "qk": 4, "silu": 5, "lm_head": 6, "empty": 7}
 
     def profile_kernel(self, kind):
