@@ -125,15 +125,33 @@ int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_bits);
  * longest context first, are cut into spans of equal length, one workgroup per (span, kv head); a sequence that several
  * spans share is merged inside the same launch by whichever of them finishes last, in span order, so results do not
  * depend on timing.  Served for head_dim 128 and decode steps (one new token per sequence); any other step runs the
- * default schedule.  Takes effect at the next step.  NVLLM_EINVAL at once for any other value. */
+ * default schedule.  NVLLM_ATTN_SHARED_PREFIX: sequences made by nvllm_seq_fork list the same leading blocks; the K/V tiles of
+ * such a shared run are streamed once per family of sequences instead of once per sequence, the family's q rows side by side
+ * in the MFMA columns that one sequence leaves idle (16 / gqa sequences per 16 columns), and each sequence's own tail by a
+ * workgroup of its own; the parts of a row are merged inside the same launch in a fixed order (shared spans ascending, then
+ * the tail), so results do not depend on timing.  Served for head_dim 128, decode steps of up to 128 sequences in which at
+ * least two sequences share a whole leading block, at every tensor-parallel size (the plan is a function of the block tables,
+ * identical on every rank); any other step runs the default schedule.
+ * Takes effect at the next step.  NVLLM_EINVAL at once for any other value. */
 #define NVLLM_ATTN_PER_SEQUENCE 0
 #define NVLLM_ATTN_BALANCED 1
+#define NVLLM_ATTN_SHARED_PREFIX 2
 int nvllm_model_set_attention_schedule(nvllm_model* m, int schedule);
 /* bytes one cached token occupies on this rank (K+V, all layers) */
 int64_t nvllm_kv_bytes_per_token(const nvllm_model* m);
 /* release a sequence's blocks (call where the reference calls BlockManager::deallocate,
  * src/engine/scheduler.rs:207,239).  Unknown seq_id is not an error. */
 int nvllm_seq_free(nvllm_model* m, int64_t seq_id);
+/* Fork: dst_seq_id becomes a live sequence with src's cached length and the same cached tokens, without a prefill (n
+ * completions of one prompt, requests behind one system prompt).  Blocks that lie wholly below src's last cached token are
+ * SHARED -- reference-counted, back on the free list when the last sequence that lists them is freed or restarted -- and
+ * never written again; the block that holds the last cached token, and any later one, is copied into fresh blocks on the
+ * library stream, so both sequences go on independently (continue dst with nvllm_step, is_prefill = 0, and its full token
+ * list).  nvllm_kv_num_free_blocks falls by that private tail only.  Every kernel reads forked sequences through their
+ * block tables; NVLLM_ATTN_SHARED_PREFIX also reads the shared blocks once per family.
+ * NVLLM_EINVAL: unknown src, or dst already live.  NVLLM_ESTATE: before nvllm_kv_alloc, or with enqueued decode steps not
+ * yet collected.  NVLLM_ENOMEM: no free sequence slot, or too few free blocks for the tail.  A failure changes nothing. */
+int nvllm_seq_fork(nvllm_model* m, int64_t src_seq_id, int64_t dst_seq_id);
 
 /* ---- step: the ModelRunner::run contract (src/engine/llm_engine.rs:145-189)
  * For each of n_seqs sequences: its id (Sequence.seq_id), its FULL token list (prompt+completion,
@@ -182,7 +200,8 @@ int nvllm_decode_next_sample(nvllm_model* m, const float* temperatures, uint64_t
 int nvllm_decode_enqueue_sample(nvllm_model* m, const float* temperatures, uint64_t seed);
 
 /* per-decode-step algorithmic HBM bytes of the LAST step on this rank:
- * weight_bytes + sum_seq ctx*kv_tok + n_seqs*kv_tok (+ 4*n_seqs*vocab when logits left the device) */
+ * weight_bytes + sum_seq ctx*kv_tok + n_seqs*kv_tok (+ 4*n_seqs*vocab when logits left the device).  Each sequence's WHOLE
+ * context is counted, also where forked sequences share blocks that NVLLM_ATTN_SHARED_PREFIX reads once. */
 int64_t nvllm_last_step_bytes(const nvllm_model* m);
 /* ---- fine seam: single ops on raw DEVICE pointers, launched on the context stream.
  * Shapes in elements; all f32 unless noted; tensors dense row-major. */

@@ -50,7 +50,8 @@ int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
  * "tile_gemm_launches" = projections run by the prefill tile GEMM; "tile_qkv_fused_launches" = QKV projections among
  * them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of the LDS-staged
  * prefill attention kernel (one per layer and prompt chunk, whatever the cache width); "attn_balanced_launches" = launches
- * of the work-balanced decode attention kernel (one per layer and decode step that qualifies); "kv_f16_saturated" = elements of the K/V pool at the
+ * of the work-balanced decode attention kernel (one per layer and decode step that qualifies); "attn_shared_launches" = launches
+ * of the shared-prefix decode attention kernel (one per layer and decode step in which forked sequences share a block); "kv_f16_saturated" = elements of the K/V pool at the
  * f16 clamp (every cache write saturates at +-65504; a scan of the pool, off the hot path); "kv_f16_absmax_bits" = the
  * largest magnitude the pool holds, as f16 bits */
 int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value);

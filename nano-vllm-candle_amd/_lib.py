@@ -65,6 +65,7 @@ _SIGS = {
     "nvllm_kv_num_free_blocks": (C.c_int, [_vp]),
     "nvllm_kv_bytes_per_token": (C.c_int64, [_vp]),
     "nvllm_seq_free": (C.c_int, [_vp, C.c_int64]),
+    "nvllm_seq_fork": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "nvllm_step": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_uint32)),
                              C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "nvllm_step_sample": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_int32), C.c_int,

@@ -504,6 +504,17 @@ struct nvllm_model {
     bool bal_on = false;            // the chunk in flight runs the balanced schedule (its plan is on the device)
     int bal_spans = 1;
     int64_t attn_balanced_launches = 0;
+    // shared-prefix decode attention (opt-in): the plan of the resident decode batch, built on the host from the block tables
+    // (plan_attn_shared) when the batch changes.  shp_plan holds items, members and rowinfo back to back; the partials grow
+    // with the plan (shp_slots), the tickets are the balanced schedule's (one schedule runs at a time).
+    AttnShared shp;
+    int* shp_plan = nullptr;
+    size_t shp_plan_ints = 0, shp_slots = 0;
+    std::vector<int> shp_host, row_slot_h, row_pos_h;  // host copy of the plan; slot and position of the resident rows
+    bool shp_valid = false;  // shp describes the rows on the device
+    bool shp_on = false;     // the chunk in flight runs the shared-prefix kernel
+    int64_t attn_shared_launches = 0;
+    std::vector<int> block_refs;  // sequences that list each block (nvllm_seq_fork shares whole blocks of a common prefix)
     float* part_val = nullptr;  // fused LM-head arg-max partials [V_l/16][max_seqs]
     int* part_idx = nullptr;
     unsigned long long* argmax_scratch = nullptr;  // ticket + per-row keys of argmax_parts_kernel
@@ -647,12 +658,17 @@ static void free_kv(nvllm_model* m) {
     m->kcache.clear(); m->vcache.clear(); m->vlocache.clear(); m->klocache.clear();
     void* ptrs[] = {m->d_block_tables, m->d_ids, m->d_pos, m->d_slot, m->d_tile_row0, m->d_tile_nrows, m->d_tile_slot,
                     m->d_last_rows, m->d_tile_order, m->d_tile_last, m->d_group_order, m->resid, m->slabs, m->qbuf, m->logits, m->d_maxval, m->red, m->xh, m->xl, m->xh2, m->xl2, m->ctxh, m->ctxl, m->ssqA, m->ssqB, m->d_next,
-                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps, m->d_samp_temps, m->d_samp_base, m->part_sval, m->part_sidx};
+                    m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps, m->d_samp_temps, m->d_samp_base, m->part_sval, m->part_sidx,
+                    m->shp_plan, m->shp.part_o, m->shp.part_ml};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     m->d_block_tables = nullptr; m->d_ids = nullptr; m->d_pos = m->d_slot = m->d_tile_row0 = m->d_tile_nrows = m->d_tile_slot = m->d_last_rows = m->d_tile_order = m->d_tile_last = m->d_group_order = nullptr;
     m->resid = m->slabs = m->qbuf = m->logits = m->d_maxval = m->red = nullptr; m->xh = m->xl = m->xh2 = m->xl2 = m->ctxh = m->ctxl = nullptr; m->ssqA = m->ssqB = nullptr; m->d_next = nullptr; m->part_val = nullptr; m->part_idx = nullptr; m->argmax_scratch = nullptr; m->attn_po = m->attn_pml = nullptr;
     m->bal = AttnBalance();
     m->bal_on = false;
+    m->shp = AttnShared();
+    m->shp_plan = nullptr;
+    m->shp_plan_ints = m->shp_slots = 0;
+    m->shp_valid = m->shp_on = false;
     m->tap_h = m->tap_res = nullptr; m->cosv = m->sinv = nullptr; m->tickets = nullptr; m->qkv_out = nullptr; m->d_keys = nullptr; m->d_temps = nullptr;
     m->d_samp_temps = m->part_sval = nullptr; m->d_samp_base = nullptr; m->part_sidx = nullptr;
     if (m->samp_pin) (void)hipHostFree(m->samp_pin);
@@ -930,6 +946,7 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
     }
     m->free_blocks.resize(num_blocks);
     for (int i = 0; i < num_blocks; ++i) m->free_blocks[i] = num_blocks - 1 - i;  // pop_back hands out 0,1,2,...
+    m->block_refs.assign(num_blocks, 0);
     m->free_slots.resize(max_seqs);
     for (int i = 0; i < max_seqs; ++i) m->free_slots[i] = max_seqs - 1 - i;
     m->h_block_tables.assign((size_t)max_seqs * m->max_blocks, 0);
@@ -993,6 +1010,10 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
         if (!rc) HIPCHK(ctx, hipMemsetAsync(m->bal.tickets, 0, (size_t)max_seqs * m->kv_l * sizeof(unsigned), ctx->stream));
         if (!rc) rc = dmalloc(ctx, &m->bal.part_o, (size_t)2 * m->bal.max_spans * m->nh_l * m->hd);
         if (!rc) rc = dmalloc(ctx, &m->bal.part_ml, (size_t)2 * m->bal.max_spans * m->nh_l * 2);
+        // shared-prefix schedule: at most bal_auto_spans + max_seqs shared items (plan_attn_shared), max_seqs members and rows;
+        // its partials are sized from the plan when one is built
+        m->shp_plan_ints = (size_t)8 * (m->bal_auto_spans + max_seqs) + (size_t)5 * max_seqs;
+        if (!rc) rc = dmalloc(ctx, &m->shp_plan, m->shp_plan_ints);
     }
     // one partial per LM-head wave: at most V_l/16 n-tiles rounded up to whole workgroups (<= 8 waves each)
     if (!rc) rc = dmalloc(ctx, &m->part_val, (size_t)(m->V_l / 16 + 16) * max_seqs);
@@ -1040,7 +1061,8 @@ extern "C" int64_t nvllm_kv_bytes_per_token(const nvllm_model* m) {
 }
 
 static void release_seq(nvllm_model* m, SeqState& s) {
-    for (int b : s.blocks) m->free_blocks.push_back(b);
+    for (int b : s.blocks)
+        if (--m->block_refs[b] == 0) m->free_blocks.push_back(b);  // a block shared by forks returns with its last reference
     s.blocks.clear();
     s.cached = 0;
 }
@@ -1054,6 +1076,55 @@ extern "C" int nvllm_seq_free(nvllm_model* m, int64_t seq_id) {
     m->seqs.erase(it);
     m->last_ids.clear();
     m->decode_resident = false;
+    return NVLLM_OK;
+}
+
+// dst becomes a live copy of src: the blocks that lie wholly below the last cached token are shared (one more reference
+// each), the block that holds it -- where a step with nothing new rewrites K/V and where decode appends -- and any later
+// one are copied into fresh blocks.  A shared block is therefore never written again and nothing has to copy on write.
+extern "C" int nvllm_seq_fork(nvllm_model* m, int64_t src_seq_id, int64_t dst_seq_id) {
+    if (!m) return NVLLM_EINVAL;
+    nvllm_ctx* ctx = m->ctx;
+    if (!m->num_blocks) return fail(ctx, NVLLM_ESTATE, "nvllm_kv_alloc not called");
+    if (!m->pending.empty()) return fail(ctx, NVLLM_ESTATE, "collect the enqueued decode steps first");
+    auto it = m->seqs.find(src_seq_id);
+    if (it == m->seqs.end()) return fail(ctx, NVLLM_EINVAL, "fork: unknown source sequence %lld", (long long)src_seq_id);
+    if (m->seqs.count(dst_seq_id)) return fail(ctx, NVLLM_EINVAL, "fork: sequence %lld is already live", (long long)dst_seq_id);
+    const SeqState& src = it->second;
+    const int n_blocks = (int)src.blocks.size();
+    const int n_shared = std::min(n_blocks, std::max(0, src.cached - 1) / kBlockTokens);  // (b + 1) * 256 <= cached - 1
+    if (m->free_slots.empty()) return fail(ctx, NVLLM_ENOMEM, "no free sequence slots (max_seqs %d)", m->max_seqs);
+    if ((int)m->free_blocks.size() < n_blocks - n_shared)
+        return fail(ctx, NVLLM_ENOMEM, "KV pool exhausted (%zu free blocks, the fork's private tail needs %d)", m->free_blocks.size(), n_blocks - n_shared);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SeqState d;
+    d.cached = src.cached;
+    d.blocks.assign(src.blocks.begin(), src.blocks.begin() + n_shared);
+    // the private tail, plane by plane: a block is contiguous per layer and plane
+    const size_t blk_elems = (size_t)m->kv_l * kBlockTokens * m->hd;
+    hipError_t e = hipSuccess;
+    for (int b = n_shared; b < n_blocks; ++b) {
+        const int from = src.blocks[b], to = m->free_blocks[m->free_blocks.size() - 1 - (size_t)(b - n_shared)];
+        d.blocks.push_back(to);
+        for (int l = 0; l < m->L && e == hipSuccess; ++l) {
+            e = hipMemcpyAsync(m->kcache[l] + to * blk_elems, m->kcache[l] + from * blk_elems, blk_elems * 2, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(m->vcache[l] + to * blk_elems, m->vcache[l] + from * blk_elems, blk_elems * 2, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess && !m->vlocache.empty())
+                e = hipMemcpyAsync(m->vlocache[l] + to * blk_elems, m->vlocache[l] + from * blk_elems, blk_elems, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess && !m->klocache.empty())
+                e = hipMemcpyAsync(m->klocache[l] + to * blk_elems, m->klocache[l] + from * blk_elems, blk_elems, hipMemcpyDeviceToDevice, ctx->stream);
+        }
+    }
+    HIPCHK(ctx, e);  // nothing below can fail: the books change only once the copies are on the stream
+    m->free_blocks.resize(m->free_blocks.size() - (size_t)(n_blocks - n_shared));
+    d.slot = m->free_slots.back();
+    m->free_slots.pop_back();
+    for (int b = 0; b < n_blocks; ++b) {
+        if (b < n_shared) ++m->block_refs[d.blocks[b]];
+        else m->block_refs[d.blocks[b]] = 1;
+        m->h_block_tables[(size_t)d.slot * m->max_blocks + b] = d.blocks[b];
+    }
+    m->seqs.emplace(dst_seq_id, d);
     return NVLLM_OK;
 }
 
@@ -1300,7 +1371,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         qa.kv.k = m->kcache[l]; qa.kv.v = m->vcache[l]; qa.kv.kv_l = m->kv_l; qa.kv.hd = hd;
         qa.kv.vlo = m->vlocache.empty() ? nullptr : m->vlocache[l];
         qa.kv.klo = m->klocache.empty() ? nullptr : m->klocache[l];
-        const bool fuse_qk = qt == 1 && n_tiles == R && !m->opt_no_attn_prologue;
+        const bool fuse_qk = qt == 1 && n_tiles == R && !m->opt_no_attn_prologue && !m->shp_on;  // the shared-prefix kernel reads qbuf
         if (!fuse_qk) PROF(m, PROF_QK, launch_qk_norm_rope_kvwrite(qa, R, s));
         AttnArgs aa;
         aa.q = m->qbuf; aa.kv = qa.kv; aa.block_tables = m->d_block_tables; aa.max_blocks = m->max_blocks;
@@ -1322,6 +1393,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         STAMPS(aa, m);
         if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
+        else if (m->shp_on) { PROF(m, PROF_ATTN, launch_attn_shared(aa, m->shp, R, s)); ++m->attn_shared_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // o_proj (+ residual + post-attention norm prep; qwen3.rs:278, :393)
         int rc = row_linear(fp.o, w.o, m->ctxh, m->ctxl, KO, w.ln2, m->ssqA, packed);
@@ -1407,8 +1479,104 @@ static int plan_attn_balanced(nvllm_model* m, int R, int n_tiles, int qt) {
     return NVLLM_OK;
 }
 
+// Shared-prefix schedule: does this chunk qualify, and does any family of its sequences share a leading run of blocks?  The
+// plan (AttnShared, kernels.h) is a pure function of the block tables and the batch, so it is the same on every TP rank and
+// is built only when the rows on the device change (upload_chunk clears shp_valid): the fast path's steps re-use it.
+static int plan_attn_shared(nvllm_model* m, int R, int n_tiles, int qt) {
+    nvllm_ctx* ctx = m->ctx;
+    m->shp_on = false;
+    if (m->opt_attn_schedule != NVLLM_ATTN_SHARED_PREFIX || qt != 1 || n_tiles != R || R > m->max_seqs || R > kFusedMaxRows || m->hd != 128 ||
+        (int)m->row_slot_h.size() != R)
+        return NVLLM_OK;
+    if (m->shp_valid) { m->shp_on = m->shp.n_shared > 0; return NVLLM_OK; }
+    std::vector<int> n_blk(m->max_seqs, 0);
+    for (const auto& kv : m->seqs) n_blk[kv.second.slot] = (int)kv.second.blocks.size();
+    auto table = [&](int row) { return m->h_block_tables.data() + (size_t)m->row_slot_h[row] * m->max_blocks; };
+    // families: rows whose first block is the same one, in order of first appearance; a block counts for a row only if it
+    // lies wholly below the row's new token
+    std::vector<std::vector<int>> fam;
+    std::unordered_map<int, int> fam_of;
+    std::vector<int> lim(R);
+    for (int r = 0; r < R; ++r) {
+        lim[r] = std::min(n_blk[m->row_slot_h[r]], m->row_pos_h[r] / kBlockTokens);
+        if (lim[r] < 1) continue;
+        auto ins = fam_of.emplace(table(r)[0], (int)fam.size());
+        if (ins.second) fam.emplace_back();
+        fam[ins.first->second].push_back(r);
+    }
+    const int cap = attn_shared_slab_rows(m->gqa, !m->vlocache.empty());
+    struct Fam { int idx, run_tiles, slabs; };
+    std::vector<Fam> use;
+    int64_t slab_tiles = 0;
+    for (int f = 0; f < (int)fam.size(); ++f) {
+        if (fam[f].size() < 2) continue;
+        int run = m->max_blocks;
+        for (int r : fam[f]) run = std::min(run, lim[r]);
+        for (int b = 1; b < run; ++b)
+            for (int r : fam[f])
+                if (table(r)[b] != table(fam[f][0])[b]) run = b;
+        const int slabs = ((int)fam[f].size() + cap - 1) / cap;
+        use.push_back({f, run * (kBlockTokens / 32), slabs});
+        slab_tiles += (int64_t)slabs * run * (kBlockTokens / 32);
+    }
+    // spans: the shared items alone fill the chip (two workgroups per CU over the local kv heads, as plan_attn_balanced's
+    // spans do); the private items are a few tiles each and run in their shadow
+    const int avail = std::max(1, m->bal_auto_spans);
+    const int span_len = std::max<int>(kAttnSharedSpanFloor, (int)((slab_tiles + avail - 1) / avail));
+    std::vector<int> items, members, rowinfo((size_t)R * 4, 0);
+    int slots = 0;
+    for (const Fam& u : use) {
+        const std::vector<int>& rows = fam[u.idx];
+        const int n_spans = (u.run_tiles + span_len - 1) / span_len;
+        for (int sl = 0; sl < u.slabs; ++sl) {
+            const int first = sl * cap, n_mem = std::min(cap, (int)rows.size() - first), mem_off = (int)members.size();
+            for (int j = 0; j < n_mem; ++j) {
+                const int r = rows[first + j];
+                members.push_back(r);
+                rowinfo[(size_t)r * 4 + 0] = slots + j; rowinfo[(size_t)r * 4 + 1] = n_mem;
+                rowinfo[(size_t)r * 4 + 2] = n_spans;   rowinfo[(size_t)r * 4 + 3] = u.run_tiles;
+            }
+            for (int sp = 0; sp < n_spans; ++sp) {
+                const int t0 = (int)((int64_t)u.run_tiles * sp / n_spans), t1 = (int)((int64_t)u.run_tiles * (sp + 1) / n_spans);
+                const int rec[8] = {mem_off, n_mem, t0, t1, slots, m->row_slot_h[rows[first]], n_spans, 0};
+                items.insert(items.end(), rec, rec + 8);
+                slots += n_mem;
+            }
+        }
+    }
+    const int n_shared = (int)items.size() / 8;
+    m->shp_valid = true;
+    m->shp.n_shared = n_shared;
+    if (n_shared == 0) return NVLLM_OK;
+    const size_t items_at = 0, members_at = items.size(), rowinfo_at = members_at + members.size();
+    if (rowinfo_at + rowinfo.size() > m->shp_plan_ints) return fail(ctx, NVLLM_EINVAL, "shared-prefix plan of %d items exceeds its buffer", n_shared);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the previous plan's host copy and partials may still be in use
+    if ((size_t)slots + R > m->shp_slots) {
+        if (m->shp.part_o) (void)hipFree(m->shp.part_o);
+        if (m->shp.part_ml) (void)hipFree(m->shp.part_ml);
+        m->shp.part_o = m->shp.part_ml = nullptr;
+        m->shp_slots = 0;
+        int rc = dmalloc(ctx, &m->shp.part_o, ((size_t)slots + R) * m->nh_l * m->hd);
+        if (!rc) rc = dmalloc(ctx, &m->shp.part_ml, ((size_t)slots + R) * m->nh_l * 2);
+        if (rc) { m->shp_valid = false; return rc; }
+        m->shp_slots = (size_t)slots + R;
+    }
+    m->shp_host = items;
+    m->shp_host.insert(m->shp_host.end(), members.begin(), members.end());
+    m->shp_host.insert(m->shp_host.end(), rowinfo.begin(), rowinfo.end());
+    HIPCHK(ctx, hipMemcpyAsync(m->shp_plan, m->shp_host.data(), m->shp_host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    m->shp.items = m->shp_plan + items_at;
+    m->shp.members = m->shp_plan + members_at;
+    m->shp.rowinfo = m->shp_plan + rowinfo_at;
+    m->shp.priv_base = slots;
+    m->shp.tickets = m->bal.tickets;
+    m->shp_on = true;
+    return NVLLM_OK;
+}
+
 static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last, int logits_row0) {
     { const int rcb = plan_attn_balanced(m, R, n_tiles, qt); if (rcb) return rcb; }
+    { const int rcs = plan_attn_shared(m, R, n_tiles, qt); if (rcs) return rcs; }
     FusedPlan fp;
     if (fused_plan(m, R, fp)) return forward_chunk_fused(m, fp, R, n_tiles, qt, n_last, logits_row0);
     nvllm_ctx* ctx = m->ctx;
@@ -1462,7 +1630,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         qa.kv.k = m->kcache[l]; qa.kv.v = m->vcache[l]; qa.kv.kv_l = m->kv_l; qa.kv.hd = hd;
         qa.kv.vlo = m->vlocache.empty() ? nullptr : m->vlocache[l];
         qa.kv.klo = m->klocache.empty() ? nullptr : m->klocache[l];
-        const bool fuse_qk = qt == 1 && n_tiles == R;  // decode: every q-tile is one row
+        const bool fuse_qk = qt == 1 && n_tiles == R && !m->shp_on;  // decode: every q-tile is one row (the shared-prefix kernel reads qbuf)
         int rcg = NVLLM_OK;
         if (t_qkv_fused && !fuse_qk) {
             // prompt chunk: q/k-norm + RoPE + KV write + q output in the QKV GEMM's epilogue (one wave tile = one head)
@@ -1493,6 +1661,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         STAMPS(aa, m);
         if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
+        else if (m->shp_on) { PROF(m, PROF_ATTN, launch_attn_shared(aa, m->shp, R, s)); ++m->attn_shared_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // output projection (qwen3.rs:278) + TP all-reduce
         int o_slabs = 1;
@@ -1576,6 +1745,7 @@ static int ensure_blocks(nvllm_model* m, SeqState& s, int len) {
         const int b = m->free_blocks.back();
         m->free_blocks.pop_back();
         m->h_block_tables[(size_t)s.slot * m->max_blocks + s.blocks.size()] = b;
+        m->block_refs[b] = 1;
         s.blocks.push_back(b);
     }
     return NVLLM_OK;
@@ -1699,6 +1869,9 @@ static int upload_chunk(nvllm_model* m, const RowPlan& p, int r0, int R, int t0,
     for (int i = 0; i < T; ++i) h_tl[i] = p.tile_nrows[t0 + i] > 0 ? p.pos[p.tile_row0[t0 + i] + p.tile_nrows[t0 + i] - 1] : -1;
     for (int i = 0; i < T; ++i) h_ord[i] = i;
     std::stable_sort(h_ord, h_ord + T, [&](int x, int y) { return h_tl[x] > h_tl[y]; });
+    m->row_slot_h.assign(h_slot, h_slot + R);  // what plan_attn_shared reads; the rows changed, so its plan is stale
+    m->row_pos_h.assign(h_pos, h_pos + R);
+    m->shp_valid = false;
     HIPCHK(ctx, hipMemcpyAsync(m->d_ids, h_ids, (size_t)R * 4, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemcpyAsync(m->d_pos, h_pos, (size_t)R * 4, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemcpyAsync(m->d_slot, h_slot, (size_t)R * 4, hipMemcpyHostToDevice, s));
@@ -1786,6 +1959,9 @@ static int step_impl(nvllm_model* m, int n_seqs, const int64_t* seq_ids, const u
         SeqState& s = it->second;
         if (s.cached >= lens[i]) s.cached = lens[i] - 1;  // nothing new: recompute the last token
         start[i] = s.cached;
+        // a block that forks share is never written: the first new token lies in the private tail unless the caller cut the list
+        if ((size_t)(start[i] / kBlockTokens) < s.blocks.size() && m->block_refs[s.blocks[start[i] / kBlockTokens]] > 1)
+            return fail(ctx, NVLLM_EINVAL, "sequence %d: tokens from %d on lie in a block shared with a fork (restart it with is_prefill)", i, start[i]);
         int rc = ensure_blocks(m, s, lens[i]);
         if (rc) return rc;
     }
@@ -1912,6 +2088,7 @@ static int decode_core(nvllm_model* m, const float* temperatures = nullptr, uint
     if (m->decode_resident) {
         // ids <- last greedy ids, pos += 1: the batch metadata is already on the device
         HIPCHK(ctx, launch_advance_decode(m->d_ids, m->d_next, m->d_pos, n, s));
+        for (int& p : m->row_pos_h) ++p;
     } else {
         // previous step was a prefill (or a multi-chunk step): rebuild decode metadata once
         RowPlan p;
@@ -2030,8 +2207,8 @@ extern "C" int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_b
 
 extern "C" int nvllm_model_set_attention_schedule(nvllm_model* m, int schedule) {
     if (!m) return NVLLM_EINVAL;
-    if (schedule != NVLLM_ATTN_PER_SEQUENCE && schedule != NVLLM_ATTN_BALANCED)
-        return fail(m->ctx, NVLLM_EINVAL, "attention schedule is NVLLM_ATTN_PER_SEQUENCE (0) or NVLLM_ATTN_BALANCED (1), not %d", schedule);
+    if (schedule != NVLLM_ATTN_PER_SEQUENCE && schedule != NVLLM_ATTN_BALANCED && schedule != NVLLM_ATTN_SHARED_PREFIX)
+        return fail(m->ctx, NVLLM_EINVAL, "attention schedule is NVLLM_ATTN_PER_SEQUENCE (0), NVLLM_ATTN_BALANCED (1) or NVLLM_ATTN_SHARED_PREFIX (2), not %d", schedule);
     m->opt_attn_schedule = schedule;  // read by the next step
     return NVLLM_OK;
 }
@@ -2065,7 +2242,8 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
 // counters for tests: "oneshot_calls" = all-reduces this model's context has run on the one-shot device path;
 // "tile_gemm_launches" = projections this model has run on the prefill tile GEMM; "tile_qkv_fused_launches" = QKV
 // projections among them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of
-// the LDS-staged prefill attention kernel; "attn_balanced_launches" = launches of the work-balanced decode attention kernel
+// the LDS-staged prefill attention kernel; "attn_balanced_launches" = launches of the work-balanced decode attention kernel;
+// "attn_shared_launches" = launches of the shared-prefix decode attention kernel
 extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value) {
     if (!m || !name || !value) return NVLLM_EINVAL;
     if (!strcmp(name, "oneshot_calls")) { *value = (int64_t)m->ctx->os_calls; return NVLLM_OK; }
@@ -2073,6 +2251,7 @@ extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t
     if (!strcmp(name, "tile_qkv_fused_launches")) { *value = m->tile_qkv_fused_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_prefill_launches")) { *value = m->attn_prefill_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_balanced_launches")) { *value = m->attn_balanced_launches; return NVLLM_OK; }
+    if (!strcmp(name, "attn_shared_launches")) { *value = m->attn_shared_launches; return NVLLM_OK; }
     if (!strcmp(name, "kv_f16_saturated") || !strcmp(name, "kv_f16_absmax_bits")) {
         // scan of the whole K/V pool (debug, off the hot path): elements the f16_sat clamp of a cache write produced, and the
         // largest magnitude stored (f16 bits; 0x7BFF = 65504 is the clamp)

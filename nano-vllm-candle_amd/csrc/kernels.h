@@ -313,6 +313,34 @@ hipError_t launch_attn_plan(const int* pos, const int* order, int rows, int span
 // a: as for the fused decode launch_attn_paged (qkv != nullptr, tile_order set); the split-KV fields are not used
 hipError_t launch_attn_balanced(const AttnArgs& a, const AttnBalance& b, int rows, int spans, hipStream_t s);
 
+// ---- shared-prefix decode attention (opt-in schedule; head_dim 128, q from the row kernel, one row per sequence) ----
+// Sequences forked from one parent (nvllm_seq_fork) list the same leading blocks in their block tables.  A family's q rows
+// fill the 16 MFMA columns that one sequence leaves idle (column c of a sub-tile = member c / gqa, q head c % gqa), so one
+// wave-load of a shared K/V tile serves 16 / gqa sequences per sub-tile.  The grid's x axis is a list of work items, y the
+// kv head: first the SHARED items (one slab of a family's members x one span of the family's shared tiles, no causal mask:
+// every shared token precedes every query), then one PRIVATE item per row (its tiles from the end of the shared run to
+// pos, taken from AttnArgs::pos like every decode kernel; a row of no family has an empty run).  The plan is built on the
+// host from the block tables when the batch changes; positions advancing on the device do not move it.
+//   items[i][8]   = first entry in members, members of the slab, first tile, end tile, first partial slot of this item
+//                   (member j's partial is slot + j), sequence slot whose block table is walked, spans of the family, 0
+//   rowinfo[r][4] = partial slot of row r in its slab's first span, slots between two spans, spans, shared tiles
+// Every contributor of a row with a shared run stores (m, l, un-normalised O) -- the private part at slot priv_base + row --
+// and draws a ticket on (row, kv head); the last arrival merges shared spans ascending, then the private part.
+struct AttnShared {
+    const int* items = nullptr;
+    const int* members = nullptr;
+    const int* rowinfo = nullptr;
+    int n_shared = 0, priv_base = 0;
+    unsigned* tickets = nullptr;  // [rows][kv_l], zero between launches
+    float* part_o = nullptr;      // [priv_base + rows][nh_l][hd]
+    float* part_ml = nullptr;     // [priv_base + rows][nh_l][2]
+};
+constexpr int kAttnSharedSpanFloor = 8;  // fewest tiles per shared span: one K/V block
+// sequences one shared item carries: q sub-tiles per workgroup (by cache width, from the register budget) x 16 / gqa
+int attn_shared_slab_rows(int gqa, bool v24);
+// a: as for launch_attn_paged's decode form without the fused prologue (q set, qkv == nullptr, tile_order set)
+hipError_t launch_attn_shared(const AttnArgs& a, const AttnShared& sp, int rows, hipStream_t s);
+
 // ---- row-parallel projection with residual + next-norm epilogue (decode, tp == 1) ---------------------
 // resid_out = resid_in + x.W^T ; x' = next_w (.) resid_out as bf16 hi/lo ; ssq[group][row] partial sums of squares.
 // One workgroup owns 16 rows x (NWN*16) features for the WHOLE K (waves split K, reduced through LDS), all loads

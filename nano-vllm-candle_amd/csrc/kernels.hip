@@ -3344,6 +3344,373 @@ hipError_t launch_attn_balanced(const AttnArgs& a, const AttnBalance& b, int row
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Shared-prefix decode attention (AttnShared, kernels.h).  The tile loop is the decode kernels' (1 KiB wave-loads straight
+// to VGPRs, waves on alternate tiles, S^T = K.q^T and O^T += V^T.P on the 16x16x32 MFMAs with q and P as f16 hi + lo,
+// per-lane online softmax) with QT q sub-tiles behind every K/V fragment: a fragment is loaded once and multiplied with
+// the q rows of QT * 16 / gqa sequences.  A shared item and a private item run the same body; the private one is a slab of
+// one member with the causal limit of its row.  q comes from the row kernel's buffer, so the new token's K/V is ordered
+// by the launch boundary.
+// ---------------------------------------------------------------------------------------------------
+// q sub-tiles of a shared item, from hipcc's resource report at two waves per SIMD (256 registers).  16-bit cache: two, with
+// one tile set in flight per wave (q and O of the second sub-tile take the 64 registers of a second set; two sets as well
+// need 357).  24-bit cache: one, one set in flight as in attn_balanced_kernel (the residual planes take the rest).  The
+// private item of the 16-bit cache keeps the decode kernels' two sets in flight.
+template <int VLO> struct AttnSharedQt { static constexpr int value = VLO ? 1 : 2; };
+
+template <int HD>
+__device__ __forceinline__ void attn_shared_merge(const AttnArgs& a, const AttnShared& sp, int row, int kh) {
+    const int* ri = sp.rowinfo + (size_t)row * 4;
+    const int slot0 = ri[0], stride = ri[1], n_spans = ri[2];
+    const int gqa = a.gqa, ldq = a.nh_l * HD;
+    // fixed order, whoever merges: shared spans ascending, then the private part
+    auto part = [&](int p, int head) { return (size_t)(p < n_spans ? slot0 + p * stride : sp.priv_base + row) * a.nh_l + head; };
+    for (int item = threadIdx.x; item < gqa * (HD / 4); item += 256) {
+        const int head = kh * gqa + item / (HD / 4), c4 = (item % (HD / 4)) * 4;
+        float mm = -1e30f;
+        for (int p = 0; p <= n_spans; ++p) mm = fmaxf(mm, sp.part_ml[part(p, head) * 2]);
+        float lt = 0.f;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int p = 0; p <= n_spans; ++p) {
+            const size_t ps = part(p, head);
+            const float fp = exp2f(sp.part_ml[ps * 2] - mm);
+            const float4 v = *reinterpret_cast<const float4*>(sp.part_o + ps * HD + c4);
+            lt += sp.part_ml[ps * 2 + 1] * fp;
+            acc.x += v.x * fp; acc.y += v.y * fp; acc.z += v.z * fp; acc.w += v.w * fp;
+        }
+        const float inv = 1.0f / lt;
+        uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
+        split_bf16(acc.x * inv, h0, l0); split_bf16(acc.y * inv, h1, l1); split_bf16(acc.z * inv, h2, l2); split_bf16(acc.w * inv, h3, l3);
+        const int col = head * HD + c4;
+        const size_t xo = a.out_packed ? xpack_off(row, col, ldq >> 5) : (size_t)row * ldq + col;
+        *reinterpret_cast<uint2*>(a.out_hi + xo) = make_uint2(h0 | ((uint32_t)h1 << 16), h2 | ((uint32_t)h3 << 16));
+        *reinterpret_cast<uint2*>(a.out_lo + xo) = make_uint2(l0 | ((uint32_t)l1 << 16), l2 | ((uint32_t)l3 << 16));
+    }
+}
+
+template <int HD, int VLO, int QT, bool PRIV>
+__device__ __forceinline__ void attn_shared_item(const AttnArgs& a, const AttnShared& sp, int item, int kh, float* ml, f32x4* obuf,
+                                                 unsigned* flags) {
+    constexpr int NWV = 4, DC = HD / 32, DT = HD / 16, DL = VLO ? DT / 2 : 1;
+    constexpr bool KLO = VLO == 2;
+    constexpr bool ONE_SET = VLO != 0 || QT > 1;  // tile sets in flight per wave: see AttnSharedQt
+    constexpr int RL = DL + (KLO ? DC : 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, grp = lane >> 4;
+    const int gqa = a.gqa, per = 16 / gqa, kv_l = a.kv.kv_l, ldq = a.nh_l * HD;
+    int mem_off = 0, n_mem = 1, t_begin, t_end, pslot0, bt_slot, n_spans, row0 = 0, pos = 0x7fffffff;
+    if constexpr (PRIV) {
+        row0 = a.tile_order[item - sp.n_shared];
+        pos = a.pos[row0];
+        t_begin = sp.rowinfo[(size_t)row0 * 4 + 3];
+        t_end = (pos >> 5) + 1;  // > t_begin: a shared block lies wholly below pos
+        n_spans = sp.rowinfo[(size_t)row0 * 4 + 2];
+        pslot0 = sp.priv_base + row0;
+        bt_slot = a.tile_slot[row0];
+    } else {
+        const int* it = sp.items + (size_t)item * 8;
+        mem_off = it[0]; n_mem = it[1]; t_begin = it[2]; t_end = it[3]; pslot0 = it[4]; bt_slot = it[5]; n_spans = it[6];
+    }
+    // MFMA column l15 of sub-tile j = (member j * per + l15 / gqa of the slab, q head l15 % gqa of this kv head)
+    const int cm = l15 / gqa, my_head = kh * gqa + (l15 - cm * gqa);
+    int rowj[QT], lim[QT];  // lim: the last token the column attends to, -1 for an idle column
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        const int mi = j * per + cm;
+        rowj[j] = PRIV ? row0 : sp.members[mem_off + min(mi, n_mem - 1)];
+        lim[j] = (cm < per && mi < n_mem) ? pos : -1;
+    }
+    const int* bt = a.block_tables + (size_t)bt_slot * a.max_blocks;
+    const _Float16* kbase = reinterpret_cast<const _Float16*>(a.kv.k);
+    const _Float16* vbase = reinterpret_cast<const _Float16*>(a.kv.v);
+    // tile kt if the item holds it, else the shared dummy tile: the same instruction stream with no K/V traffic
+    auto load_tile_or_dummy = [&](int kt, uint4 (&ka)[DC], uint4 (&kb2)[DC], uint4 (&vf)[DT], uint4 (&vl)[RL]) {
+        const bool real = kt < t_end;
+        const int T0 = min(kt, t_end - 1) << 5;
+        const int blk = bt[T0 >> 8], tb = T0 & 255;
+        const size_t slab = (size_t)(blk * kv_l + kh) * kBlockTokens * HD;
+        const _Float16* dummy = reinterpret_cast<const _Float16*>(g_attn_dummy_tile) + lane * 8;
+        const _Float16* kb = real ? kbase + slab + (size_t)(tb >> 4) * (DC * 512) + lane * 8 : dummy;
+        const _Float16* vb = real ? vbase + slab + (size_t)(tb >> 5) * (DT * 512) + lane * 8 : dummy;
+#pragma unroll
+        for (int c = 0; c < DC; ++c) {
+            ka[c] = ld_stream16(kb + c * 512);
+            kb2[c] = ld_stream16(kb + (DC + c) * 512);
+        }
+#pragma unroll
+        for (int d = 0; d < DT; ++d) vf[d] = ld_stream16(vb + d * 512);
+        if constexpr (VLO) {
+            const uint8_t* vlb = real ? a.kv.vlo + slab + (size_t)(tb >> 5) * (DL * 1024) + lane * 16
+                                      : reinterpret_cast<const uint8_t*>(g_attn_dummy_tile) + lane * 16;
+#pragma unroll
+            for (int d = 0; d < DL; ++d) vl[d] = ld_stream16(vlb + d * 1024);
+        }
+        if constexpr (KLO) {
+            const uint8_t* klb = real ? a.kv.klo + slab + (size_t)(tb >> 4) * ((DC / 2) * 1024) + lane * 16
+                                      : reinterpret_cast<const uint8_t*>(g_attn_dummy_tile) + lane * 16;
+#pragma unroll
+            for (int i = 0; i < DC; ++i) vl[DL + i] = ld_stream16(klb + i * 1024);
+        }
+    };
+
+    // ---- gather the slab's q rows (already normalised, rotated and scaled) as f16 hi + lo B fragments
+    f16x8 qh[QT][DC], ql[QT][DC];
+    [[maybe_unused]] long q8[QT][DC];
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        const float* pq = a.q + (size_t)rowj[j] * ldq + (size_t)my_head * HD + grp * 8;
+#pragma unroll
+        for (int c = 0; c < DC; ++c) {
+            float x[8];
+            *reinterpret_cast<float4*>(&x[0]) = *reinterpret_cast<const float4*>(pq + c * 32);
+            *reinterpret_cast<float4*>(&x[4]) = *reinterpret_cast<const float4*>(pq + c * 32 + 4);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float y = lim[j] >= 0 ? x[i] : 0.f;
+                const _Float16 h = (_Float16)y;
+                qh[j][c][i] = h;
+                ql[j][c][i] = (_Float16)(y - (float)h);
+            }
+            if constexpr (KLO) {
+                int w0 = 0, w1 = 0;
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[j][c][0], (float)qh[j][c][1], w0, false);
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[j][c][2], (float)qh[j][c][3], w0, true);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[j][c][4], (float)qh[j][c][5], w1, false);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)qh[j][c][6], (float)qh[j][c][7], w1, true);
+                q8[j][c] = (long)(((unsigned long long)(unsigned)w1 << 32) | (unsigned)w0);
+            }
+        }
+    }
+    f32x4 o[QT][DT];
+    float m[QT], lsum[QT];
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        m[j] = -1e30f;
+        lsum[j] = 0.f;
+#pragma unroll
+        for (int d = 0; d < DT; ++d) o[j][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    auto compute_tile = [&](int kt, const uint4 (&ka)[DC], const uint4 (&kb2)[DC], const uint4 (&vf)[DT], const uint4 (&vl)[RL]) {
+        const int T0 = kt << 5;
+        const int tokA = T0 + grp * 4, tokB = T0 + 16 + grp * 4;
+        f32x4 sa[QT], sb[QT];
+#pragma unroll
+        for (int j = 0; j < QT; ++j) sa[j] = sb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < DC; ++c) {
+            const f16x8 fa = __builtin_bit_cast(f16x8, ka[c]);
+            const f16x8 fb = __builtin_bit_cast(f16x8, kb2[c]);
+#pragma unroll
+            for (int j = 0; j < QT; ++j) {
+                sa[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, qh[j][c], sa[j], 0, 0, 0);
+                sa[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, ql[j][c], sa[j], 0, 0, 0);
+                sb[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, qh[j][c], sb[j], 0, 0, 0);
+                sb[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, ql[j][c], sb[j], 0, 0, 0);
+                if constexpr (KLO) {  // the K residual bytes are bf8 numbers: A operands as they are, fenced from the f16 MFMAs
+                    const uint4 pa = vl[DL + (c >> 1)], pb = vl[DL + DC / 2 + (c >> 1)];
+                    const unsigned long long la = (c & 1) ? ((unsigned long long)pa.w << 32) | pa.z : ((unsigned long long)pa.y << 32) | pa.x;
+                    const unsigned long long lb = (c & 1) ? ((unsigned long long)pb.w << 32) | pb.z : ((unsigned long long)pb.y << 32) | pb.x;
+                    mfma_result_settled(sa[j]);
+                    mfma_result_settled(sb[j]);
+                    sa[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)la, q8[j][c], sa[j], 0, 0, 0);
+                    sb[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)lb, q8[j][c], sb[j], 0, 0, 0);
+                    mfma_result_settled(sa[j]);
+                    mfma_result_settled(sb[j]);
+                }
+            }
+        }
+        f16x8 P[QT], Pl[QT];  // P as f16 hi + f16 lo (22 bits), see attn_paged_kernel
+        float alpha[QT];
+        [[maybe_unused]] long P8[QT];
+#pragma unroll
+        for (int j = 0; j < QT; ++j) {
+            float mt = -1e30f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (tokA + r <= lim[j]) mt = fmaxf(mt, sa[j][r]);
+                if (tokB + r <= lim[j]) mt = fmaxf(mt, sb[j][r]);
+            }
+            mt = fmaxf(mt, __shfl_xor(mt, 16));
+            mt = fmaxf(mt, __shfl_xor(mt, 32));
+            const float mn = fmaxf(m[j], mt);
+            alpha[j] = exp2f(m[j] - mn);
+            m[j] = mn;
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pa = (tokA + r <= lim[j]) ? exp2f(sa[j][r] - mn) : 0.f;
+                const float pb = (tokB + r <= lim[j]) ? exp2f(sb[j][r] - mn) : 0.f;
+                ps += pa + pb;
+                P[j][r] = (_Float16)pa;
+                P[j][4 + r] = (_Float16)pb;
+                Pl[j][r] = (_Float16)(pa - (float)P[j][r]);
+                Pl[j][4 + r] = (_Float16)(pb - (float)P[j][4 + r]);
+            }
+            lsum[j] = lsum[j] * alpha[j] + ps;
+            if constexpr (VLO) {
+                int w0 = 0, w1 = 0;
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[j][0], (float)P[j][1], w0, false);
+                w0 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[j][2], (float)P[j][3], w0, true);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[j][4], (float)P[j][5], w1, false);
+                w1 = __builtin_amdgcn_cvt_pk_bf8_f32((float)P[j][6], (float)P[j][7], w1, true);
+                P8[j] = (long)(((unsigned long long)(unsigned)w1 << 32) | (unsigned)w0);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < DT; ++d) {
+            const f16x8 fv = __builtin_bit_cast(f16x8, vf[d]);
+#pragma unroll
+            for (int j = 0; j < QT; ++j) {
+                f32x4 acc = o[j][d];
+                acc[0] *= alpha[j]; acc[1] *= alpha[j]; acc[2] *= alpha[j]; acc[3] *= alpha[j];
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, P[j], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fv, Pl[j], acc, 0, 0, 0);
+                if constexpr (VLO) {  // the V residual bytes against P in bf8
+                    const uint4 pr = vl[d >> 1];
+                    const unsigned long long lo8 = (d & 1) ? ((unsigned long long)pr.w << 32) | pr.z : ((unsigned long long)pr.y << 32) | pr.x;
+                    mfma_result_settled(acc);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)lo8, P8[j], acc, 0, 0, 0);
+                }
+                o[j][d] = acc;
+            }
+        }
+    };
+    {
+        // each wave takes every fourth tile of the item; a set is refilled right after it is consumed, unconditionally:
+        // past the item's end the refill reads the dummy tile
+        uint4 kaA[DC], kbA[DC], vfA[DT], vlA[RL];
+        int kt = t_begin + wave;
+        load_tile_or_dummy(kt, kaA, kbA, vfA, vlA);
+        if constexpr (ONE_SET) {
+            while (kt < t_end) {
+                compute_tile(kt, kaA, kbA, vfA, vlA);
+                load_tile_or_dummy(kt + NWV, kaA, kbA, vfA, vlA);
+                kt += NWV;
+            }
+        } else {
+            uint4 kaB[DC], kbB[DC], vfB[DT], vlB[RL];
+            load_tile_or_dummy(kt + NWV, kaB, kbB, vfB, vlB);
+            while (kt < t_end) {
+                compute_tile(kt, kaA, kbA, vfA, vlA);
+                load_tile_or_dummy(kt + 2 * NWV, kaA, kbA, vfA, vlA);
+                kt += NWV;
+                if (kt >= t_end) break;
+                compute_tile(kt, kaB, kbB, vfB, vlB);
+                load_tile_or_dummy(kt + 2 * NWV, kaB, kbB, vfB, vlB);
+                kt += NWV;
+            }
+        }
+    }
+
+    // ---- the four waves' (m, l, O) through LDS, one sub-tile after the other; then the row's output or its partial
+    const bool whole = PRIV && n_spans == 0;  // uniform: a sequence that shares nothing, no ticket
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        const bool valid = lim[j] >= 0;
+        float ls = lsum[j];
+        ls += __shfl_xor(ls, 16);
+        ls += __shfl_xor(ls, 32);
+        if (grp == 0) {
+            ml[(wave * 2 + 0) * 16 + l15] = m[j];
+            ml[(wave * 2 + 1) * 16 + l15] = ls;
+        }
+        __syncthreads();
+        float ms = -1e30f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) ms = fmaxf(ms, ml[(w * 2 + 0) * 16 + l15]);
+        float ltot = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) ltot += ml[(w * 2 + 1) * 16 + l15] * exp2f(ml[(w * 2 + 0) * 16 + l15] - ms);
+        {
+            const float fs = exp2f(m[j] - ms);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                f32x4 v = o[j][d];
+                v[0] *= fs; v[1] *= fs; v[2] *= fs; v[3] *= fs;
+                obuf[(wave * DT + d) * 64 + lane] = v;
+            }
+        }
+        __syncthreads();
+        const int row = rowj[j];
+        const size_t pslot = (size_t)(pslot0 + (PRIV ? 0 : j * per + cm)) * a.nh_l + my_head;
+        for (int d = wave; d < DT; d += NWV) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < NWV; ++w) {
+                const f32x4 v = obuf[(w * DT + d) * 64 + lane];
+                acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
+            }
+            if (!valid) continue;
+            if (!whole) {
+                *reinterpret_cast<float4*>(sp.part_o + pslot * HD + d * 16 + grp * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                continue;
+            }
+            const float inv = 1.0f / ltot;
+            uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
+            split_bf16(acc[0] * inv, h0, l0); split_bf16(acc[1] * inv, h1, l1); split_bf16(acc[2] * inv, h2, l2); split_bf16(acc[3] * inv, h3, l3);
+            const int col = my_head * HD + d * 16 + grp * 4;
+            const size_t xo = a.out_packed ? xpack_off(row, col, ldq >> 5) : (size_t)row * ldq + col;
+            *reinterpret_cast<uint2*>(a.out_hi + xo) = make_uint2(h0 | ((uint32_t)h1 << 16), h2 | ((uint32_t)h3 << 16));
+            *reinterpret_cast<uint2*>(a.out_lo + xo) = make_uint2(l0 | ((uint32_t)l1 << 16), l2 | ((uint32_t)l3 << 16));
+        }
+        if (!whole && wave == 0 && grp == 0 && valid) {
+            sp.part_ml[pslot * 2 + 0] = ms;
+            sp.part_ml[pslot * 2 + 1] = ltot;
+        }
+    }
+    if (whole) return;
+    // ---- publish the partials, draw one ticket per member on (row, kv head); the last arrival of a row merges it
+    // (attn_balanced_kernel's protocol).  A workgroup that is not last for any of its rows leaves.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if ((int)threadIdx.x < n_mem) {
+        const int row = PRIV ? row0 : sp.members[mem_off + threadIdx.x];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unsigned* ticket = sp.tickets + (size_t)row * kv_l + kh;
+        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned last = t == (unsigned)n_spans ? 1u : 0u;  // n_spans shared parts + the private one
+        if (last) {
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        flags[threadIdx.x] = last;
+    }
+    __syncthreads();
+    for (int i = 0; i < n_mem; ++i)
+        if (flags[i]) attn_shared_merge<HD>(a, sp, PRIV ? row0 : sp.members[mem_off + i], kh);
+}
+
+template <int HD, int VLO>
+__global__ void __launch_bounds__(256, 2) attn_shared_kernel(AttnArgs a, AttnShared sp) {
+    __shared__ float ml[4 * 2 * 16];
+    __shared__ f32x4 obuf[4 * (HD / 16) * 64];
+    __shared__ unsigned flags[32];
+    const int item = blockIdx.x, kh = blockIdx.y;
+    if (item < sp.n_shared) attn_shared_item<HD, VLO, AttnSharedQt<VLO>::value, false>(a, sp, item, kh, ml, obuf, flags);
+    else attn_shared_item<HD, VLO, 1, true>(a, sp, item, kh, ml, obuf, flags);
+}
+
+int attn_shared_slab_rows(int gqa, bool v24) { return (v24 ? AttnSharedQt<1>::value : AttnSharedQt<0>::value) * (16 / gqa); }
+
+template <int VLO>
+static hipError_t attn_shared_launch_v(const AttnArgs& a, const AttnShared& sp, int rows, hipStream_t s) {
+    attn_shared_kernel<128, VLO><<<dim3(sp.n_shared + rows, a.kv.kv_l), 256, 0, s>>>(a, sp);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_shared(const AttnArgs& a, const AttnShared& sp, int rows, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (a.kv.hd != 128 || a.gqa < 1 || a.gqa > 16 || !a.q || a.qkv || !a.tile_order || !a.out_hi || !a.out_lo) return hipErrorInvalidValue;
+    if (!sp.items || !sp.members || !sp.rowinfo || !sp.tickets || !sp.part_o || !sp.part_ml || sp.n_shared < 1) return hipErrorInvalidValue;
+    if (a.kv.klo && !a.kv.vlo) return hipErrorInvalidValue;  // 24-bit K comes with 24-bit V only
+    if (a.kv.klo) return attn_shared_launch_v<2>(a, sp, rows, s);
+    if (a.kv.vlo) return attn_shared_launch_v<1>(a, sp, rows, s);
+    return attn_shared_launch_v<0>(a, sp, rows, s);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // SwiGLU gate: SiluAndMul::forward (activation.rs:13-18): split last dim in two, silu(a)*b
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) silu_mul_kernel(const float* __restrict__ gu, int n_slabs, int64_t slab_stride,

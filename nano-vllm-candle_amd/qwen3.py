@@ -203,12 +203,14 @@ class Qwen3ForCausalLM:
         24-bit K only together with 24-bit V, and head_dim 128.  Anything else raises NvllmError (EINVAL)."""
         _lib.check(_lib.lib().nvllm_model_set_kv_cache_bits(self.h, int(k_bits), int(v_bits)), self.ctx.h)
 
-    ATTENTION_SCHEDULES = {"per_sequence": 0, "balanced": 1}
+    ATTENTION_SCHEDULES = {"per_sequence": 0, "balanced": 1, "shared_prefix": 2}
 
     def set_attention_schedule(self, schedule):
         """How decode attention is split over workgroups, from the next step on: "per_sequence" (the default: one workgroup
-        per sequence and kv head) or "balanced" (equal spans of K/V tiles whatever the sequence boundaries, merged inside
-        the launch; head_dim 128, other steps keep the default).  Anything else raises NvllmError (EINVAL)."""
+        per sequence and kv head), "balanced" (equal spans of K/V tiles whatever the sequence boundaries, merged inside
+        the launch; head_dim 128, other steps keep the default) or "shared_prefix" (the blocks that forked sequences share
+        are read once per family of sequences, seq_fork; head_dim 128, decode steps with such a family, other steps keep
+        the default).  Anything else raises NvllmError (EINVAL)."""
         code = self.ATTENTION_SCHEDULES.get(schedule, schedule if isinstance(schedule, int) else -1)
         _lib.check(_lib.lib().nvllm_model_set_attention_schedule(self.h, int(code)), self.ctx.h)
 
@@ -222,6 +224,11 @@ class Qwen3ForCausalLM:
 
     def seq_free(self, seq_id):
         _lib.check(_lib.lib().nvllm_seq_free(self.h, int(seq_id)), self.ctx.h)
+
+    def seq_fork(self, src, dst):
+        """dst becomes a live copy of sequence src without a prefill (nvllm_seq_fork): whole blocks below src's last cached
+        token are shared, the tail is copied.  Continue dst with step(..., is_prefill=False) and its full token list."""
+        _lib.check(_lib.lib().nvllm_seq_fork(self.h, int(src), int(dst)), self.ctx.h)
 
     @property
     def weight_bytes(self):
