@@ -38,6 +38,11 @@ extern "C" {
 
 #define NVLLM_DTYPE_F32 0
 #define NVLLM_DTYPE_BF16 1
+#define NVLLM_DTYPE_F8E4M3 2 /* OCP e4m3fn: bias 7, no infinity, NaN = S.1111.111, largest value 448 */
+
+/* storage of the layer projections (q/k/v, o, gate/up, down); lm_head, embedding and norms are bf16 / f32 in both */
+#define NVLLM_WEIGHTS_BF16 0
+#define NVLLM_WEIGHTS_FP8_BLOCK128 1 /* e4m3 codes + one scale per 128 x 128 block: official Qwen3 "-FP8" checkpoints */
 
 #define NVLLM_RCCL_ID_BYTES 128
 
@@ -100,6 +105,21 @@ int nvllm_model_fill_synthetic(nvllm_model* m, uint64_t seed);
  * stream) -- the statistics real Qwen3 checkpoints have; parity stress input (tests/test_stress_gpu.py). */
 int nvllm_model_fill_synthetic_profile(nvllm_model* m, uint64_t seed, int profile);
 int nvllm_model_finalize(nvllm_model* m);
+/* Storage format of the layer projections.  NVLLM_WEIGHTS_FP8_BLOCK128 halves their bytes (the weight stream of a decode
+ * step, and the memory nvllm_kv_alloc can hand to the K/V cache): e4m3 codes with one f32 scale per 128 x 128 block of the
+ * HF tensor, read by a GEMM of their own that converts codes to bf16 in registers (exactly) and applies the block scale in
+ * f32 to each block's partial sum; activations stay hi + lo bf16, so the only error is the quantisation of the weights.
+ *   before any projection tensor is loaded: the projection buffers are re-allocated in the FP8 layout;
+ *   after loading (nvllm_model_fill_synthetic* too), before nvllm_kv_alloc: every projection is quantised in place on the
+ *     device, one matrix at a time (peak: one extra matrix), scale = block amax / 448, nearest-even codes;
+ *   after nvllm_kv_alloc: NVLLM_ESTATE.  Unknown format: NVLLM_EINVAL.  Back to BF16 once FP8 data exists: NVLLM_ESTATE.
+ * nvllm_model_load_tensor on an FP8-format model takes "<proj>.weight" as NVLLM_DTYPE_F8E4M3 (raw codes, HF shape; a NaN
+ * code is NVLLM_EINVAL) together with "<proj>.weight_scale_inv" (f32 or bf16, [ceil(rows/128)][ceil(cols/128)] of the full
+ * tensor: the factor that MULTIPLIES the code, whatever the name suggests), or as f32 / bf16, quantised on load.  An F8
+ * tensor offered to a BF16-format model is NVLLM_EINVAL; nvllm_model_finalize is NVLLM_ESTATE when codes lack their scales; a
+ * tensor-parallel shard whose first column is not a multiple of 128 is NVLLM_EINVAL (no published Qwen3 shape at tp <= 8).
+ * An FP8 model runs the generic forward path at every row count (no epilogue-fused FP8 GEMMs yet). */
+int nvllm_model_set_weight_format(nvllm_model* m, int format);
 /* bytes of weights this rank reads per decode step (layers + final norm + LM head; embedding excluded) */
 int64_t nvllm_model_weight_bytes(const nvllm_model* m);
 

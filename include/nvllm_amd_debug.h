@@ -43,7 +43,8 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
  *       the local kv heads; positive values are for tests and tuning, clamped to what nvllm_kv_alloc sized the partial
  *       buffers for (four times the automatic value);
  *   "no_fused", "no_xpack", "no_rowpar", "no_attn_prologue" (default 0): force the generic decode path / row-major planes /
- *       no whole-K row-parallel GEMMs / q,k-norm + RoPE + KV write in their own row kernel. */
+ *       no whole-K row-parallel GEMMs / q,k-norm + RoPE + KV write in their own row kernel;
+ *   "weights_fp8" (0 | 1; before nvllm_kv_alloc): the debug spelling of nvllm_model_set_weight_format (nvllm_amd.h). */
 int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
 
 /* counters for tests: "oneshot_calls" = all-reduces run on the one-shot device path by this model's context;
@@ -87,6 +88,12 @@ int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt,
  * hi + lo; act_packed: the tile kernel writes its planes in fragment order. */
 int nvllm_debug_gemm_tile_check(nvllm_ctx* ctx, int M, int N, int K, int mode, int act_packed, int iters,
                                 float* max_abs_diff, float* max_abs_ref, float* us_chunked, float* us_tile);
+
+/* The FP8 weight GEMM alone (w8_gemm.hip), for its parity test: y[M,N] = x[M,K] . (scale (.) code)^T.  x, y: DEVICE f32;
+ * codes: HOST bytes [N][K] (e4m3fn); scales: HOST f32 [ceil(N/128)][ceil(K/128)], one per 128 x 128 block of the codes.
+ * N % 16 == 0, K % 128 == 0.  Runs split hi/lo -> pack -> the GEMM, up to two K slices -> slab sum. */
+int nvllm_debug_linear_fp8(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                           float* y);
 
 /* tuning aid: time the decode attention (one new token per sequence, ctx_lens[B] cached tokens each) on a
  * synthetic cache; part_tokens > 0 splits every context into workgroups of that many tokens */

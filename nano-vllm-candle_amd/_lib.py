@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("NVLLM_LIB", "libnvllm_amd.so")))
 
 OK, EINVAL, EHIP, ENOMEM, ESTATE, ERCCL = 0, -1, -2, -3, -4, -5
-DTYPE_F32, DTYPE_BF16 = 0, 1
+DTYPE_F32, DTYPE_BF16, DTYPE_F8E4M3 = 0, 1, 2
+WEIGHTS_BF16, WEIGHTS_FP8_BLOCK128 = 0, 1
 RCCL_ID_BYTES = 128
 
 
@@ -58,6 +59,7 @@ _SIGS = {
     "nvllm_model_fill_synthetic_profile": (C.c_int, [_vp, C.c_uint64, C.c_int]),
     "nvllm_model_finalize": (C.c_int, [_vp]),
     "nvllm_model_weight_bytes": (C.c_int64, [_vp]),
+    "nvllm_model_set_weight_format": (C.c_int, [_vp, C.c_int]),
     "nvllm_tp_shard": (C.c_int, [C.POINTER(Qwen3ConfigC), C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]),
     "nvllm_kv_alloc": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nvllm_model_set_kv_cache_bits": (C.c_int, [_vp, C.c_int, C.c_int]),
@@ -101,6 +103,7 @@ _SIGS = {
     "nvllm_debug_gemm_bench2": (C.c_int, [_vp] + [C.c_int] * 10 + [C.POINTER(C.c_float)]),
     "nvllm_debug_get_counter": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_int64)]),
     "nvllm_debug_gemm_tile_check": (C.c_int, [_vp] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 4),
+    "nvllm_debug_linear_fp8": (C.c_int, [_vp, _fp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _fp]),
     "nvllm_debug_xcc_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nvllm_debug_attn_bench": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "nvllm_dev_alloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
@@ -111,7 +114,8 @@ _SIGS = {
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _DEBUG_EXPORTS_ADDED_LATER = ("nvllm_debug_stamps", "nvllm_debug_stamps_read", "nvllm_ctx_create_null_comm", "nvllm_debug_set_option",
                               "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter", "nvllm_model_set_attention_schedule",
-                              "nvllm_decode_next_sample", "nvllm_decode_enqueue_sample")
+                              "nvllm_decode_next_sample", "nvllm_decode_enqueue_sample", "nvllm_model_set_weight_format",
+                              "nvllm_debug_linear_fp8")
 
 _lib = None
 

@@ -425,6 +425,7 @@ constexpr int kAttnMaxParts = 64;  // split-KV partitions per sequence (partitio
 
 struct LayerW {
     PackedW qkv, o, gu, down;
+    PackedW8 qkv8, o8, gu8, down8;  // NVLLM_WEIGHTS_FP8_BLOCK128: the projections live here (the bf16 buffers are released)
     float *ln1 = nullptr, *ln2 = nullptr, *qn = nullptr, *kn = nullptr;
 };
 
@@ -443,6 +444,8 @@ struct nvllm_model {
     float* norm = nullptr;
     std::vector<LayerW> layers;
     std::unordered_map<std::string, bool> loaded;
+    int weight_format = NVLLM_WEIGHTS_BF16;         // nvllm_model_set_weight_format
+    std::unordered_map<std::string, bool> f8_codes;  // projections loaded as checkpoint codes: finalize wants their scales
     bool finalized = false;
     float *cosv = nullptr, *sinv = nullptr;
     int rope_len = 0;
@@ -691,6 +694,7 @@ extern "C" int nvllm_model_destroy(nvllm_model* m) {
     (void)hipFree(m->embed); (void)hipFree(m->lm_head.data); (void)hipFree(m->norm);
     for (auto& w : m->layers) {
         (void)hipFree(w.qkv.data); (void)hipFree(w.o.data); (void)hipFree(w.gu.data); (void)hipFree(w.down.data);
+        for (PackedW8* w8 : {&w.qkv8, &w.o8, &w.gu8, &w.down8}) { (void)hipFree(w8->codes); (void)hipFree(w8->scales); }
         (void)hipFree(w.ln1); (void)hipFree(w.ln2); (void)hipFree(w.qn); (void)hipFree(w.kn);
     }
     delete m;
@@ -702,6 +706,8 @@ extern "C" int nvllm_model_destroy(nvllm_model* m) {
 struct Target {
     enum Kind { PACKED, F32VEC, BF16ROWS } kind = PACKED;
     PackedW* w = nullptr;
+    PackedW8* w8 = nullptr;  // layer projections: the same matrix in the FP8 layout
+    bool is_scale = false;   // "<proj>.weight_scale_inv": full shape = the tensor's 128 x 128 blocks, region as the weight's
     float* f = nullptr;
     bf16_bits* b = nullptr;
     int64_t full_rows = 0, full_cols = 0;  // HF shape
@@ -725,18 +731,27 @@ static bool resolve(nvllm_model* m, const char* name, Target& t) {
     if (!strcmp(name, "model.norm.weight")) {
         t.kind = Target::F32VEC; t.f = m->norm; t.full_rows = 1; t.full_cols = H; t.rows = 1; t.cols = H; t.synth_kind = kSynthNorm; t.synth_axis = kSynthAxisCol; return true;
     }
+    // "<proj>.weight_scale_inv" (FP8 checkpoints): the projection's own target and shard region, flagged
+    static const char kScaleSuffix[] = "_scale_inv";
+    const size_t nl = strlen(name), sl = sizeof kScaleSuffix - 1;
+    if (nl > sl && nl < 200 && !strcmp(name + nl - sl, kScaleSuffix)) {
+        const std::string base(name, nl - sl);
+        if (!resolve(m, base.c_str(), t) || !t.w8) return false;
+        t.is_scale = true;
+        return true;
+    }
     int l = -1, off = 0;
     if (sscanf(name, "model.layers.%d.%n", &l, &off) != 1 || l < 0 || l >= m->L || off == 0) return false;
     const char* s = name + off;
     LayerW& w = m->layers[l];
     const int64_t qr = (int64_t)m->nh_l * hd, kr = (int64_t)m->kv_l * hd;
-    if (!strcmp(s, "self_attn.q_proj.weight")) { t.w = &w.qkv; t.full_rows = nh * hd; t.full_cols = H; t.r0 = rank * qr; t.rows = qr; t.cols = H; t.dst_row0 = 0; return true; }
-    if (!strcmp(s, "self_attn.k_proj.weight")) { t.w = &w.qkv; t.full_rows = kv * hd; t.full_cols = H; t.r0 = rank * kr; t.rows = kr; t.cols = H; t.dst_row0 = (int)qr; return true; }
-    if (!strcmp(s, "self_attn.v_proj.weight")) { t.w = &w.qkv; t.full_rows = kv * hd; t.full_cols = H; t.r0 = rank * kr; t.rows = kr; t.cols = H; t.dst_row0 = (int)(qr + kr); return true; }
-    if (!strcmp(s, "self_attn.o_proj.weight")) { t.w = &w.o; t.full_rows = H; t.full_cols = nh * hd; t.c0 = rank * qr; t.rows = H; t.cols = qr; t.synth_axis = kSynthAxisRow; return true; }
-    if (!strcmp(s, "mlp.gate_proj.weight")) { t.w = &w.gu; t.full_rows = I; t.full_cols = H; t.r0 = (int64_t)rank * m->I_l; t.rows = m->I_l; t.cols = H; t.dst_row0 = 0; t.ileave = 0; return true; }
-    if (!strcmp(s, "mlp.up_proj.weight")) { t.w = &w.gu; t.full_rows = I; t.full_cols = H; t.r0 = (int64_t)rank * m->I_l; t.rows = m->I_l; t.cols = H; t.dst_row0 = 0; t.ileave = 1; return true; }
-    if (!strcmp(s, "mlp.down_proj.weight")) { t.w = &w.down; t.full_rows = H; t.full_cols = I; t.c0 = (int64_t)rank * m->I_l; t.rows = H; t.cols = m->I_l; t.synth_axis = kSynthAxisRow; return true; }
+    if (!strcmp(s, "self_attn.q_proj.weight")) { t.w = &w.qkv; t.w8 = &w.qkv8; t.full_rows = nh * hd; t.full_cols = H; t.r0 = rank * qr; t.rows = qr; t.cols = H; t.dst_row0 = 0; return true; }
+    if (!strcmp(s, "self_attn.k_proj.weight")) { t.w = &w.qkv; t.w8 = &w.qkv8; t.full_rows = kv * hd; t.full_cols = H; t.r0 = rank * kr; t.rows = kr; t.cols = H; t.dst_row0 = (int)qr; return true; }
+    if (!strcmp(s, "self_attn.v_proj.weight")) { t.w = &w.qkv; t.w8 = &w.qkv8; t.full_rows = kv * hd; t.full_cols = H; t.r0 = rank * kr; t.rows = kr; t.cols = H; t.dst_row0 = (int)(qr + kr); return true; }
+    if (!strcmp(s, "self_attn.o_proj.weight")) { t.w = &w.o; t.w8 = &w.o8; t.full_rows = H; t.full_cols = nh * hd; t.c0 = rank * qr; t.rows = H; t.cols = qr; t.synth_axis = kSynthAxisRow; return true; }
+    if (!strcmp(s, "mlp.gate_proj.weight")) { t.w = &w.gu; t.w8 = &w.gu8; t.full_rows = I; t.full_cols = H; t.r0 = (int64_t)rank * m->I_l; t.rows = m->I_l; t.cols = H; t.dst_row0 = 0; t.ileave = 0; return true; }
+    if (!strcmp(s, "mlp.up_proj.weight")) { t.w = &w.gu; t.w8 = &w.gu8; t.full_rows = I; t.full_cols = H; t.r0 = (int64_t)rank * m->I_l; t.rows = m->I_l; t.cols = H; t.dst_row0 = 0; t.ileave = 1; return true; }
+    if (!strcmp(s, "mlp.down_proj.weight")) { t.w = &w.down; t.w8 = &w.down8; t.full_rows = H; t.full_cols = I; t.c0 = (int64_t)rank * m->I_l; t.rows = H; t.cols = m->I_l; t.synth_axis = kSynthAxisRow; return true; }
     t.kind = Target::F32VEC; t.synth_kind = kSynthNorm; t.full_rows = 1; t.rows = 1;
     if (!strcmp(s, "input_layernorm.weight")) { t.f = w.ln1; t.full_cols = t.cols = H; t.synth_axis = kSynthAxisCol; return true; }
     if (!strcmp(s, "post_attention_layernorm.weight")) { t.f = w.ln2; t.full_cols = t.cols = H; t.synth_axis = kSynthAxisCol; return true; }
@@ -753,13 +768,99 @@ static inline uint16_t host_f32_to_bf16(float f) {  // round-to-nearest-even (ex
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+// ---- FP8 projections (NVLLM_WEIGHTS_FP8_BLOCK128) ----------------------------------------------------
+static int alloc_w8(nvllm_ctx* ctx, PackedW8& w, int N, int K) {
+    w.N = N; w.K = K;
+    HIPCHK(ctx, hipMalloc((void**)&w.codes, w.code_bytes()));
+    HIPCHK(ctx, hipMalloc((void**)&w.scales, w.scale_bytes()));
+    return NVLLM_OK;
+}
+static void free_w8(PackedW8& w) {
+    (void)hipFree(w.codes); (void)hipFree(w.scales);
+    w.codes = nullptr; w.scales = nullptr;
+}
+
+// One scale per 128 x 128 block of a [rows][cols] tensor -> the PackedW8 scale plane: every 16-row tile of the region
+// (tensor rows r0.., column blocks c0 / 128..) takes the scale of the block it came from.  dst_row0 / ileave as the codes.
+static hipError_t upload_w8_scales(const PackedW8& w, const float* blocks, int64_t block_cols, int64_t r0, int64_t c0, int rows,
+                                   int dst_row0, int ileave) {
+    const int tiles = rows / 16, KB = w.K / 128;
+    std::vector<float> e((size_t)tiles * KB);
+    for (int ti = 0; ti < tiles; ++ti)
+        for (int kb = 0; kb < KB; ++kb) e[(size_t)ti * KB + kb] = blocks[(size_t)((r0 + 16 * ti) / 128) * block_cols + c0 / 128 + kb];
+    float* dst = w.scales + (size_t)(ileave < 0 ? dst_row0 / 16 : ileave) * KB;
+    return hipMemcpy2D(dst, (size_t)(ileave < 0 ? 1 : 2) * KB * 4, e.data(), (size_t)KB * 4, (size_t)KB * 4, tiles, hipMemcpyHostToDevice);
+}
+
+// a projection tensor (or its scale tensor) of an FP8-format model; shapes are checked by the caller
+static int load_tensor_w8(nvllm_model* m, const Target& t, const char* hf_name, const void* host_data, int dtype) {
+    nvllm_ctx* ctx = m->ctx;
+    if (t.c0 % 128 || t.r0 % 16 || t.cols != t.w8->K)
+        return fail(ctx, NVLLM_EINVAL, "tensor '%s': this rank's shard starts at column %lld, not at a 128-column scale block", hf_name, (long long)t.c0);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (t.is_scale) {
+        const int64_t br = (t.full_rows + 127) / 128, bc = (t.full_cols + 127) / 128;
+        std::vector<float> blocks((size_t)br * bc);
+        for (size_t i = 0; i < blocks.size(); ++i) {
+            if (dtype == NVLLM_DTYPE_F32) blocks[i] = ((const float*)host_data)[i];
+            else { uint32_t u = (uint32_t)((const uint16_t*)host_data)[i] << 16; memcpy(&blocks[i], &u, 4); }
+        }
+        HIPCHK(ctx, upload_w8_scales(*t.w8, blocks.data(), bc, t.r0, t.c0, (int)t.rows, t.dst_row0, t.ileave));
+        return NVLLM_OK;
+    }
+    const size_t n = (size_t)t.rows * t.cols;
+    void* dtmp = nullptr;
+    hipError_t e;
+    if (dtype == NVLLM_DTYPE_F8E4M3) {
+        const uint8_t* src = (const uint8_t*)host_data;
+        for (size_t i = 0, total = (size_t)t.full_rows * t.full_cols; i < total; ++i)
+            if ((src[i] & 0x7Fu) == 0x7Fu) return fail(ctx, NVLLM_EINVAL, "tensor '%s': NaN code at element %zu", hf_name, i);
+        std::vector<uint8_t> tmp(n);
+        for (int64_t r = 0; r < t.rows; ++r) memcpy(&tmp[(size_t)r * t.cols], src + (size_t)(t.r0 + r) * t.full_cols + t.c0, (size_t)t.cols);
+        HIPCHK(ctx, hipMalloc(&dtmp, n));
+        e = hipMemcpy(dtmp, tmp.data(), n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_pack_codes_w8(*t.w8, t.dst_row0, (int)t.rows, (const uint8_t*)dtmp, t.cols, t.ileave, ctx->stream);
+        m->f8_codes[hf_name] = true;
+    } else {  // quantised on load, by the kernel of the in-place conversion
+        std::vector<uint16_t> tmp(n);
+        for (int64_t r = 0; r < t.rows; ++r)
+            for (int64_t c = 0; c < t.cols; ++c) {
+                const size_t si = (size_t)(t.r0 + r) * t.full_cols + (t.c0 + c);
+                tmp[(size_t)r * t.cols + c] = dtype == NVLLM_DTYPE_F32 ? host_f32_to_bf16(((const float*)host_data)[si]) : ((const uint16_t*)host_data)[si];
+            }
+        HIPCHK(ctx, hipMalloc(&dtmp, n * 2));
+        e = hipMemcpy(dtmp, tmp.data(), n * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = launch_quant_pack_w8(*t.w8, t.dst_row0, (int)t.rows, (int)(t.r0 % 128), (const bf16_bits*)dtmp, t.cols, nullptr, t.ileave, ctx->stream);
+        m->f8_codes.erase(hf_name);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dtmp);
+    HIPCHK(ctx, e);
+    return NVLLM_OK;
+}
+
 extern "C" int nvllm_model_load_tensor(nvllm_model* m, const char* hf_name, const void* host_data, int dtype,
                                        const int64_t* shape, int ndim) {
     if (!m || !hf_name || !host_data || !shape) return fail(m ? m->ctx : nullptr, NVLLM_EINVAL, "NULL argument");
     nvllm_ctx* ctx = m->ctx;
-    if (dtype != NVLLM_DTYPE_F32 && dtype != NVLLM_DTYPE_BF16) return fail(ctx, NVLLM_EINVAL, "dtype %d unsupported", dtype);
+    if (dtype != NVLLM_DTYPE_F32 && dtype != NVLLM_DTYPE_BF16 && dtype != NVLLM_DTYPE_F8E4M3) return fail(ctx, NVLLM_EINVAL, "dtype %d unsupported", dtype);
     Target t;
     if (!resolve(m, hf_name, t)) return fail(ctx, NVLLM_EINVAL, "unknown tensor name '%s'", hf_name);
+    const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;
+    if ((dtype == NVLLM_DTYPE_F8E4M3 || t.is_scale) && !fp8)
+        return fail(ctx, NVLLM_EINVAL, "tensor '%s': FP8 codes and block scales need an FP8-format model (nvllm_model_set_weight_format)", hf_name);
+    if (dtype == NVLLM_DTYPE_F8E4M3 && (!t.w8 || t.is_scale))
+        return fail(ctx, NVLLM_EINVAL, "tensor '%s': only the layer projections are stored as FP8 codes", hf_name);
+    if (fp8 && t.w8) {
+        const int64_t want_r = t.is_scale ? (t.full_rows + 127) / 128 : t.full_rows, want_c = t.is_scale ? (t.full_cols + 127) / 128 : t.full_cols;
+        if (ndim != 2 || shape[0] != want_r || shape[1] != want_c)
+            return fail(ctx, NVLLM_EINVAL, "tensor '%s': shape mismatch (want %lld x %lld)", hf_name, (long long)want_r, (long long)want_c);
+        const int rc8 = load_tensor_w8(m, t, hf_name, host_data, dtype);
+        if (rc8) return rc8;
+        m->loaded[hf_name] = true;
+        return NVLLM_OK;
+    }
     int64_t rows = ndim == 2 ? shape[0] : 1, cols = ndim == 2 ? shape[1] : (ndim == 1 ? shape[0] : -1);
     if (ndim == 2 && t.kind == Target::F32VEC && shape[0] == 1) { rows = 1; cols = shape[1]; }  // [1,H] norm weight (qwen3.rs:180)
     if (cols != t.full_cols || rows != t.full_rows)
@@ -811,6 +912,16 @@ static int synth_one(nvllm_model* m, const char* name, uint64_t seed, int profil
         HIPCHK(ctx, launch_synth_rowmajor_f32(t.f, sp, 0, t.cols, ctx->stream));
     } else if (t.kind == Target::BF16ROWS) {
         HIPCHK(ctx, launch_synth_rowmajor_bf16(t.b, sp, 0, t.rows * t.cols, ctx->stream));
+    } else if (t.w8 && m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128) {
+        // generated as bf16 where its rows will go, then quantised like a loaded matrix (peak: this one matrix)
+        PackedW tmp;
+        tmp.N = t.w->N; tmp.K = t.w->K;
+        HIPCHK(ctx, hipMalloc((void**)&tmp.data, tmp.bytes()));
+        hipError_t e = launch_synth_packed(tmp, t.dst_row0, (int)t.rows, sp, t.r0, t.c0, t.full_cols, t.ileave, ctx->stream);
+        if (e == hipSuccess) e = launch_quant_pack_w8(*t.w8, t.dst_row0, (int)t.rows, (int)(t.r0 % 128), nullptr, 0, &tmp, t.ileave, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(tmp.data);
+        HIPCHK(ctx, e);
     } else {
         HIPCHK(ctx, launch_synth_packed(*t.w, t.dst_row0, (int)t.rows, sp, t.r0, t.c0, t.full_cols, t.ileave, ctx->stream));
     }
@@ -873,6 +984,8 @@ extern "C" int nvllm_model_finalize(nvllm_model* m) {
         for (const char* s : kLayerTensors) {
             snprintf(name, sizeof name, "model.layers.%d.%s", l, s);
             if (!m->loaded.count(name)) return fail(ctx, NVLLM_ESTATE, "missing tensor %s", name);
+            if (m->f8_codes.count(name) && !m->loaded.count(std::string(name) + "_scale_inv"))
+                return fail(ctx, NVLLM_ESTATE, "tensor %s was loaded as FP8 codes but %s_scale_inv is missing", name, name);
         }
     if (!m->loaded.count("lm_head.weight")) {
         // tied embeddings: LM head = this rank's vocab rows of the embedding table
@@ -886,9 +999,62 @@ extern "C" int nvllm_model_finalize(nvllm_model* m) {
 extern "C" int64_t nvllm_model_weight_bytes(const nvllm_model* m) {
     if (!m) return 0;
     int64_t b = (int64_t)m->lm_head.bytes() + (int64_t)m->H * 4;
+    const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;  // codes + expanded scales: what the GEMM reads
     for (const auto& w : m->layers)
-        b += (int64_t)(w.qkv.bytes() + w.o.bytes() + w.gu.bytes() + w.down.bytes()) + (int64_t)(2 * m->H + 2 * m->hd) * 4;
+        b += (int64_t)(fp8 ? w.qkv8.bytes() + w.o8.bytes() + w.gu8.bytes() + w.down8.bytes()
+                           : w.qkv.bytes() + w.o.bytes() + w.gu.bytes() + w.down.bytes()) + (int64_t)(2 * m->H + 2 * m->hd) * 4;
     return b;
+}
+
+extern "C" int nvllm_model_set_weight_format(nvllm_model* m, int format) {
+    if (!m) return NVLLM_EINVAL;
+    nvllm_ctx* ctx = m->ctx;
+    if (format != NVLLM_WEIGHTS_BF16 && format != NVLLM_WEIGHTS_FP8_BLOCK128)
+        return fail(ctx, NVLLM_EINVAL, "weight format is NVLLM_WEIGHTS_BF16 (0) or NVLLM_WEIGHTS_FP8_BLOCK128 (1), not %d", format);
+    if (m->num_blocks > 0) return fail(ctx, NVLLM_ESTATE, "the weight format is set before nvllm_kv_alloc");
+    if (format == m->weight_format) return NVLLM_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    char name[160];
+    if (format == NVLLM_WEIGHTS_BF16) {
+        for (int l = 0; l < m->L; ++l)
+            for (int i = 0; i < 7; ++i) {
+                snprintf(name, sizeof name, "model.layers.%d.%s", l, kLayerTensors[i]);
+                if (m->loaded.count(name)) return fail(ctx, NVLLM_ESTATE, "FP8 projections are loaded: they do not go back to bf16");
+            }
+        for (LayerW& w : m->layers) {
+            PackedW* ws[4] = {&w.qkv, &w.o, &w.gu, &w.down};
+            PackedW8* w8s[4] = {&w.qkv8, &w.o8, &w.gu8, &w.down8};
+            for (int k = 0; k < 4; ++k) {
+                free_w8(*w8s[k]);
+                HIPCHK(ctx, hipMalloc((void**)&ws[k]->data, ws[k]->bytes()));
+            }
+        }
+        m->weight_format = format;
+        return NVLLM_OK;
+    }
+    // one matrix at a time: FP8 buffers, the loaded tensors of the matrix quantised from its bf16 tiles, bf16 buffer released
+    static const int kFirst[5] = {0, 3, 4, 6, 7};  // kLayerTensors: q,k,v | o | gate,up | down
+    for (int l = 0; l < m->L; ++l) {
+        LayerW& w = m->layers[l];
+        PackedW* ws[4] = {&w.qkv, &w.o, &w.gu, &w.down};
+        PackedW8* w8s[4] = {&w.qkv8, &w.o8, &w.gu8, &w.down8};
+        for (int k = 0; k < 4; ++k) {
+            const int rc = alloc_w8(ctx, *w8s[k], ws[k]->N, ws[k]->K);
+            if (rc) return rc;
+            for (int i = kFirst[k]; i < kFirst[k + 1]; ++i) {
+                snprintf(name, sizeof name, "model.layers.%d.%s", l, kLayerTensors[i]);
+                Target t;
+                if (!m->loaded.count(name) || !resolve(m, name, t)) continue;
+                HIPCHK(ctx, launch_quant_pack_w8(*t.w8, t.dst_row0, (int)t.rows, (int)(t.r0 % 128), nullptr, 0, t.w, t.ileave, ctx->stream));
+            }
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            HIPCHK(ctx, hipFree(ws[k]->data));
+            ws[k]->data = nullptr;
+        }
+    }
+    m->weight_format = format;
+    return NVLLM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1209,6 +1375,7 @@ static bool fused_plan(const nvllm_model* m, int R, FusedPlan& p) {
     const int H = m->H, hd = m->hd, NQ = (m->nh_l + 2 * m->kv_l) * hd, KO = m->nh_l * hd, I2 = 2 * m->I_l;
     const bool tp = m->ctx->tp_size > 1;
     if (R > kFusedMaxRows || m->taps || m->opt_no_fused) return false;
+    if (m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128) return false;  // FP8 projections: f32 slabs only (no epilogue-fused forms yet)
     auto fits = [&](int N, int K, int epi) {
         return m->opt_stream_combine && gemm_stream_ok(R, N, K, epi) && gemm_stream_slab_floats(R, N, K, epi) <= m->slab_floats;
     };
@@ -1467,6 +1634,14 @@ static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, 
     return NVLLM_OK;
 }
 
+// the same for an FP8 projection: one kernel at every row count, as many K slices as fill the chip and fit the slab buffer
+static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW8& w, float* out, int R,
+                      int max_split, int* n_slabs) {
+    const int fit = (int)std::min<size_t>((size_t)max_split, m->slab_floats / ((size_t)R * w.N));
+    PROF(m, PROF_GEMM, launch_gemm_w8(xh, xl, ldx, w, out, R, std::max(fit, 1), n_slabs, m->ctx->stream));
+    return NVLLM_OK;
+}
+
 // rows R (ids/pos/slot/tiles already on the device), n_last rows listed in d_last_rows -> logits rows
 // Balanced schedule: does this chunk qualify, and if so put its plan on the device -- once, ahead of the layers.  The plan
 // is a function of the positions already there (uploaded, or advanced by launch_advance_decode): no host round trip.
@@ -1592,13 +1767,16 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     // big-model decode: when all four projections of a layer run the streaming GEMM, the activation planes between
     // the row kernels and the GEMMs stay in MFMA fragment order (xpack_off): x staging costs 3x per byte otherwise
     const bool no_xpack = m->opt_no_xpack != 0;
-    const int packed = !no_xpack && !m->layers.empty() && gemm_streams(m, m->layers[0].qkv, R) && gemm_streams(m, m->layers[0].o, R) &&
+    // FP8 projections: row-major planes into the one FP8 GEMM (f32 slabs); every consumer of the slabs is as for bf16
+    const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;
+    const int w8_ks = R <= kFusedMaxRows ? 16 : 8;
+    const int packed = !fp8 && !no_xpack && !m->layers.empty() && gemm_streams(m, m->layers[0].qkv, R) && gemm_streams(m, m->layers[0].o, R) &&
                        gemm_streams(m, m->layers[0].gu, R) && gemm_streams(m, m->layers[0].down, R) && m->I_l % 32 == 0;
     // prompt chunks (MFMA-bound): projections whose grid fills the chip run the tile GEMM (tile_gemm.hip); it reads both
     // operands in fragment order, so the kernel that produces its input planes writes them that way
     const int KO = m->nh_l * hd;
     const int tmin = m->opt_tile_min_wgs;
-    const bool tile_on = !packed && tmin > 0 && R > kFusedMaxRows;
+    const bool tile_on = !fp8 && !packed && tmin > 0 && R > kFusedMaxRows;
     // K splits (f32 slabs summed by the consumer): up to 4 on prompt chunks; a few hundred decode rows are MFMA-bound
     // too (hi + lo planes: 4 flops per weight byte and row) and need up to 8 to fill the chip
     const int max_ks = R <= 512 ? 8 : 4;
@@ -1638,6 +1816,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
             ++m->tile_qkv_fused_launches;
         } else {
             if (t_qkv) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.qkv, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &qa.n_slabs, s));
+            else if (fp8) rcg = gemm_slabs(m, m->xh, m->xl, H, w.qkv8, m->slabs, R, w8_ks, &qa.n_slabs);
             else rcg = gemm_slabs(m, m->xh, m->xl, H, w.qkv, m->slabs, R, 8, &qa.n_slabs, packed);
             if (rcg) return rcg;
             if (!fuse_qk) PROF(m, PROF_QK, launch_qk_norm_rope_kvwrite(qa, R, s));
@@ -1666,6 +1845,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         // output projection (qwen3.rs:278) + TP all-reduce
         int o_slabs = 1;
         if (t_o) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.o, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &o_slabs, s));
+        else if (fp8) rcg = gemm_slabs(m, m->xh, m->xl, KO, w.o8, m->slabs, R, w8_ks, &o_slabs);
         else rcg = gemm_slabs(m, m->xh, m->xl, KO, w.o, m->slabs, R, 8, &o_slabs, packed);
         if (rcg) return rcg;
         const float* oin; int ons;
@@ -1679,6 +1859,12 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         // MLP (qwen3.rs:323-327)
         if (t_gu) {
             PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.gu, R, 2, nullptr, m->xh2, m->xl2, t_down ? 1 : 0, tmin, 1, nullptr, s));
+        } else if (fp8) {
+            // FP8 gate/up: slabs of the INTERLEAVED gate/up rows, then SiLU*mul on their sum
+            int gs = 1;
+            rcg = gemm_slabs(m, m->xh, m->xl, H, w.gu8, m->slabs, R, w8_ks, &gs);
+            if (rcg) return rcg;
+            PROF(m, PROF_SILU, launch_silu_mul_interleaved(m->slabs, gs, (int64_t)R * 2 * m->I_l, R, m->I_l, m->xh2, m->xl2, 0, s));
         } else if (!packed && R <= kFusedMaxRows && gemm_rowpar_ok(2 * m->I_l, H, 1, R)) {
             // small gate/up: whole-K row-parallel kernel with the SiLU*mul epilogue
             RowParArgs rg;
@@ -1699,6 +1885,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         }
         int d_slabs = 1;
         if (t_down) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh2, m->xl2, w.down, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &d_slabs, s));
+        else if (fp8) rcg = gemm_slabs(m, m->xh2, m->xl2, m->I_l, w.down8, m->slabs, R, w8_ks, &d_slabs);
         else rcg = gemm_slabs(m, m->xh2, m->xl2, m->I_l, w.down, m->slabs, R, 8, &d_slabs, packed);
         if (rcg) return rcg;
         rc = tp_reduce(m, R, d_slabs, &prev, &prev_ns, &prev_stride);
@@ -2230,6 +2417,7 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
         m->opt_kv_v_bits = value; return NVLLM_OK;
     }
     if (!strcmp(name, "oneshot_skip_push")) { m->opt_oneshot_skip_push = std::max(0, value); return NVLLM_OK; }  // test hook
+    if (!strcmp(name, "weights_fp8")) return nvllm_model_set_weight_format(m, value ? NVLLM_WEIGHTS_FP8_BLOCK128 : NVLLM_WEIGHTS_BF16);  // before kv_alloc
     if (!strcmp(name, "no_fused")) { m->opt_no_fused = value; return NVLLM_OK; }    // decode through the generic path
     if (!strcmp(name, "no_xpack")) { m->opt_no_xpack = value; return NVLLM_OK; }    // row-major activation planes
     if (!strcmp(name, "no_rowpar")) { m->opt_no_rowpar = value; return NVLLM_OK; }  // generic path: no whole-K row-parallel GEMMs
@@ -2393,6 +2581,37 @@ extern "C" int nvllm_op_linear(nvllm_ctx* ctx, const float* x, const nvllm_weigh
     HIPCHK(ctx, launch_split_hilo_pad(x, M, w->K, Kp, hi, lo, s));
     HIPCHK(ctx, launch_gemm(p, hi, lo, Kp, w->w, slabs, M, s));
     HIPCHK(ctx, launch_slab_sum_ld(slabs, p.n_split, (int64_t)M * Np, Np, bias, M, w->N, y, w->N, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NVLLM_OK;
+}
+
+// the FP8 GEMM alone on caller-supplied codes and per-block scales (tests/test_fp8_weights_gpu.py)
+extern "C" int nvllm_debug_linear_fp8(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                                      float* y) {
+    if (!ctx || !x || !codes || !scales || !y || !gemm_w8_ok(M, N, K)) return fail(ctx, NVLLM_EINVAL, "bad linear_fp8 arguments (N %% 16, K %% 128)");
+    for (size_t i = 0; i < (size_t)N * K; ++i)
+        if ((codes[i] & 0x7Fu) == 0x7Fu) return fail(ctx, NVLLM_EINVAL, "NaN code at element %zu", i);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    TmpBufs t;
+    PackedW8 w;
+    w.N = N; w.K = K;
+    bf16_bits *hi, *lo;
+    uint8_t* dcodes;
+    float* slabs;
+    HIPCHK(ctx, t.get(&w.codes, w.code_bytes() / 16));
+    HIPCHK(ctx, t.get(&w.scales, w.scale_bytes() / 4));
+    HIPCHK(ctx, t.get(&dcodes, (size_t)N * K));
+    HIPCHK(ctx, t.get(&hi, (size_t)M * K));
+    HIPCHK(ctx, t.get(&lo, (size_t)M * K));
+    HIPCHK(ctx, t.get(&slabs, (size_t)2 * M * N));
+    HIPCHK(ctx, hipMemcpy(dcodes, codes, (size_t)N * K, hipMemcpyHostToDevice));
+    HIPCHK(ctx, upload_w8_scales(w, scales, (K + 127) / 128, 0, 0, N, 0, -1));
+    HIPCHK(ctx, launch_pack_codes_w8(w, 0, N, dcodes, K, -1, s));
+    HIPCHK(ctx, launch_split_hilo_pad(x, M, K, K, hi, lo, s));
+    int ns = 1;
+    HIPCHK(ctx, launch_gemm_w8(hi, lo, K, w, slabs, M, 2, &ns, s));
+    HIPCHK(ctx, launch_slab_sum_ld(slabs, ns, (int64_t)M * N, N, nullptr, M, N, y, N, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NVLLM_OK;
 }
@@ -2762,6 +2981,7 @@ extern "C" int nvllm_debug_xcc_map(nvllm_ctx* ctx, int gx, int gy, int gz, int t
 
 // tuning aid, v2: mode 0 = slabs, 2 = SwiGLU epilogue (N = 2I); mt = m-tiles per workgroup (0 = planner);
 // `rot` weight copies are cycled so every launch streams cold HBM like the model does (1 = cache-warm).
+// mode 8 = the FP8 weight GEMM (w8_gemm.hip) on the same matrices quantised per block; n_split = most K slices (0: 16)
 extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt, int nw, int n_split, int mode,
                                        int rot, int iters, float* us_per_call) {
     // diagnostic build: mode 22 / 23 + 100 * a = ablation variant a of the streaming kernel (stream_gemm.hip ABL)
@@ -2787,6 +3007,15 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
         HIPCHK(ctx, t.get(&ws[r].data, (size_t)N * K / 8));
         HIPCHK(ctx, launch_synth_packed(ws[r], 0, N, synth_plain(12345 + r, kSynthMatrix), 0, 0, K, -1, s));
     }
+    std::vector<PackedW8> w8s(mode == 8 ? rot : 0);
+    for (size_t r = 0; r < w8s.size(); ++r) {
+        w8s[r].N = N; w8s[r].K = K;
+        HIPCHK(ctx, t.get(&w8s[r].codes, (size_t)N * K / 16));
+        HIPCHK(ctx, t.get(&w8s[r].scales, w8s[r].scale_bytes() / 4));
+        HIPCHK(ctx, launch_quant_pack_w8(w8s[r], 0, N, 0, nullptr, 0, &ws[r], -1, s));
+    }
+    const int w8_split = std::min(n_split > 0 ? n_split : 16, 32);
+    if (mode == 8) p.n_split = 32;  // slab room for any split
     bf16_bits *xh, *xl, *ah, *al; float* out;
     HIPCHK(ctx, t.get(&xh, (size_t)M * K)); HIPCHK(ctx, t.get(&xl, (size_t)M * K));
     HIPCHK(ctx, t.get(&ah, (size_t)M * N)); HIPCHK(ctx, t.get(&al, (size_t)M * N));
@@ -2815,6 +3044,7 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
     }
     auto go = [&](int i) -> hipError_t {
         const PackedW& w = ws[i % rot];
+        if (mode == 8) { int ns = 1; return launch_gemm_w8(xh, xl, K, w8s[i % rot], out, M, w8_split, &ns, s); }
         if (mode == 20 || mode == 21) return launch_gemm_argmax(plm, xh, xl, K, w, nullptr, M, pv, pi, nullptr, s);
         if (mode == 22 || mode == 23) return launch_gemm_stream(xh, xl, K, w, out, M, mode == 23, s);  // 23: packed x planes
         if (mode >= 10) {

@@ -22,6 +22,36 @@ struct PackedW {
     size_t bytes() const { return (size_t)N * K * 2; }
 };
 
+// ---- packed FP8 weight (w8_gemm.hip): block-scaled OCP e4m3fn codes, the layout of official -FP8 checkpoints ----------
+// codes [N/16][K/64][64 lanes][16 B]: lane l of tile (nt, kp) holds the 8 codes W[nt*16 + (l&15)][kp*64 + 8*(l>>4) + 0..7],
+// then the 8 codes of the same row 32 columns further on (the A-fragments of k-tiles 2kp and 2kp+1: one 1 KiB wave-load =
+// one n-tile x two k-tiles, each 8-byte half converts to a fragment with no lane movement).
+// scales f32 [N/16][K/128]: the factor that multiplies the codes of one 16-row tile x 128-column block -- the scale of the
+// 128 x 128 checkpoint block the tile came from, expanded at load so that the q/k/v concatenation, the gate/up interleave
+// and tensor-parallel row shards need no block arithmetic in the kernel.
+struct PackedW8 {
+    uint4* codes = nullptr;
+    float* scales = nullptr;
+    int N = 0, K = 0;  // logical sizes (N % 16 == 0, K % 128 == 0)
+    size_t code_bytes() const { return (size_t)N * K; }
+    size_t scale_bytes() const { return (size_t)(N / 16) * (K / 128) * 4; }
+    size_t bytes() const { return code_bytes() + scale_bytes(); }
+};
+// out[ks][M][N] = x[M][K-slice ks] . (scales (.) codes)[N][K-slice ks]^T, f32 slabs, ks < *n_slabs <= max_split; the K
+// slices cut at multiples of 128 (a scale block is never split).  x = row-major hi + lo bf16 planes.  Any M >= 1.
+bool gemm_w8_ok(int M, int N, int K);
+hipError_t launch_gemm_w8(const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW8& w, float* out, int M, int max_split,
+                          int* n_slabs, hipStream_t s);
+// quantise rows [0, rows) of a bf16 source into rows dst row0.. (ileave as launch_pack_rows): per 128 x 128 block of the
+// SOURCE TENSOR scale = amax / 448 (1 for an all-zero block), code = nearest-even e4m3 of w / scale, saturating.  row_phase =
+// tensor row of source row 0, mod 128 (where the tensor's row blocks start; a shard that begins inside a block quantises
+// its part of that block by its own amax).  The source is row-major (src, ld) or, with src_packed, the PackedW that holds
+// the same rows at the same place (in-place conversion of a loaded matrix).
+hipError_t launch_quant_pack_w8(const PackedW8& dst, int row0, int rows, int row_phase, const bf16_bits* src, int64_t ld,
+                                const PackedW* src_packed, int ileave, hipStream_t s);
+// checkpoint codes, row-major bytes (ld % 8 == 0) -> rows dst row0.. of the code plane
+hipError_t launch_pack_codes_w8(const PackedW8& dst, int row0, int rows, const uint8_t* src, int64_t ld, int ileave, hipStream_t s);
+
 // pack rows [row0, row0+rows) of dst from a row-major bf16 source (ld = elements between rows)
 // ileave: -1 = rows land at row0.. ; 0/1 = gate(0)/up(1) rows interleaved in 16-row tiles (SwiGLU epilogue layout)
 hipError_t launch_pack_rows(const PackedW& dst, int row0, int rows, const bf16_bits* src, int64_t ld, int ileave,

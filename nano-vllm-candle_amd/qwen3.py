@@ -106,7 +106,8 @@ class Qwen3Config:
 
 def read_safetensors(path):
     """Minimal safetensors reader (header JSON + raw little-endian data, memory-mapped): yields
-    (name, np.ndarray view, dtype code).  Executes nothing from the file.  BF16 tensors come back as uint16."""
+    (name, np.ndarray view, dtype code).  Executes nothing from the file.  BF16 tensors come back as uint16, F8_E4M3 tensors
+    (the projection weights of FP8 checkpoints) as their uint8 codes."""
     with open(path, "rb") as f:
         n = struct.unpack("<Q", f.read(8))[0]
         header = json.loads(f.read(n))
@@ -120,11 +121,26 @@ def read_safetensors(path):
             arr, code = data[b:e].view(np.uint16), _lib.DTYPE_BF16
         elif dt == "F32":
             arr, code = data[b:e].view(np.float32), _lib.DTYPE_F32
+        elif dt == "F8_E4M3":
+            arr, code = data[b:e], _lib.DTYPE_F8E4M3
         elif dt == "F16":
             arr, code = data[b:e].view(np.float16).astype(np.float32), _lib.DTYPE_F32
         else:
             raise ValueError(f"{path}: tensor {name} has unsupported dtype {dt}")
         yield name, arr.reshape(meta["shape"]), code
+
+
+def hf_weight_format(model_dir):
+    """"fp8" for a checkpoint whose config.json carries quantization_config {quant_method: "fp8", weight_block_size:
+    [128, 128]} (the official Qwen3 -FP8 checkpoints), "bf16" without quantization_config; any other quantisation raises"""
+    with open(os.path.join(model_dir, "config.json")) as f:
+        q = json.load(f).get("quantization_config")
+    if not q:
+        return "bf16"
+    if q.get("quant_method") == "fp8" and list(q.get("weight_block_size") or []) == [128, 128]:
+        return "fp8"
+    raise ValueError(f"{model_dir}: unsupported quantization_config {q!r} (only quant_method 'fp8' with weight_block_size "
+                     "[128, 128] is served)")
 
 
 def checkpoint_files(model_dir):
@@ -144,7 +160,9 @@ def checkpoint_files(model_dir):
 class Qwen3ForCausalLM:
     """src/models/qwen3.rs:503-551"""
 
-    def __init__(self, cfg, ctx=None):
+    WEIGHT_FORMATS = {"bf16": _lib.WEIGHTS_BF16, "fp8": _lib.WEIGHTS_FP8_BLOCK128}
+
+    def __init__(self, cfg, ctx=None, weight_format="bf16"):
         self.cfg = cfg
         self.ctx = ctx or Context(0)
         h = C.c_void_p()
@@ -152,13 +170,22 @@ class Qwen3ForCausalLM:
         _lib.check(_lib.lib().nvllm_model_create(self.ctx.h, C.byref(cc), C.byref(h)), self.ctx.h)
         self.h = h
         self._kv = False
+        if weight_format != "bf16":
+            self.set_weight_format(weight_format)
+
+    def set_weight_format(self, weight_format):
+        """Storage of the layer projections: "bf16" (the default) or "fp8" (e4m3 codes + one scale per 128 x 128 block, half
+        the bytes, read by their own GEMM; nvllm_model_set_weight_format).  Before loading: FP8 checkpoints load as they
+        are, f32 / bf16 tensors are quantised on load.  After loading, before kv_alloc: quantised in place."""
+        code = self.WEIGHT_FORMATS.get(weight_format, weight_format if isinstance(weight_format, int) else -1)
+        _lib.check(_lib.lib().nvllm_model_set_weight_format(self.h, int(code)), self.ctx.h)
 
     # ---- construction ----
     @classmethod
     def from_hf_dir(cls, model_dir, ctx=None):
         """qwen3.rs:515-536 (+ sharded checkpoints and tied lm_head, which the reference cannot load: SURVEY F9)"""
         cfg = Qwen3Config.from_hf_dir(model_dir)
-        m = cls(cfg, ctx)
+        m = cls(cfg, ctx, hf_weight_format(model_dir))
         files = checkpoint_files(model_dir)
         for path in files:
             for name, arr, code in read_safetensors(path):

@@ -1,0 +1,19 @@
+"""CPU: every instantiation of the FP8 weight GEMM runs without scratch, and the few-rows forms (up to 64 rows, where the
+weight stream is the bound) keep at least two waves per SIMD (hipcc's own report, written beside the library by the build)."""
+import os
+
+PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nano-vllm-candle_amd", "kernel_resources_w8.txt")
+
+
+def test_fp8_gemm_kernels_keep_their_register_budget():
+    assert os.path.exists(PATH), "kernel_resources_w8.txt missing: rebuild the library (make -C nano-vllm-candle_amd/csrc)"
+    res = {}
+    for blk in open(PATH).read().split("Function Name: ")[1:]:
+        lines = blk.strip().splitlines()
+        res[lines[0].strip()] = {k.strip(): int(v) for k, v in (l.split(":", 1) for l in lines[1:])}
+    hits = {n: r for n, r in res.items() if n.startswith("_ZN5nvllm14gemm_w8_kernelILi")}
+    assert len(hits) == 6, sorted(hits)  # MT 1, 2 x NT 2, 4; MT 4, 8 x NT 2
+    for n, r in hits.items():
+        assert r["ScratchSize [bytes/lane]"] == 0, (n, r)
+        if not n.startswith("_ZN5nvllm14gemm_w8_kernelILi8E"):
+            assert r["Occupancy [waves/SIMD]"] >= 2, (n, r)

@@ -1,0 +1,41 @@
+"""The FP8 weight GEMM (w8_gemm.hip) against the bf16 slab GEMMs on the Qwen3-8B / 32B layer shapes, kernel alone:
+nvllm_debug_gemm_bench2 mode 8 (FP8) against mode 22 (streaming kernel, where it covers the shape) or mode 0 (planner's
+chunked kernel), device events around 20 launches that cycle enough weight copies to stream cold HBM, arms interleaved,
+three rounds; prints the median microseconds and the weight bytes per second of each arm."""
+import ctypes as C
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nano_vllm_candle_amd as pkg  # noqa: E402
+
+SHAPES = {"8B qkv": (6144, 4096), "8B o": (4096, 4096), "8B gate_up": (24576, 4096), "8B down": (4096, 12288),
+          "32B qkv": (10240, 5120), "32B o": (5120, 8192), "32B gate_up": (51200, 5120), "32B down": (5120, 25600)}
+
+
+def main():
+    ctx = pkg.Context(0)
+    L = pkg._lib.lib()
+
+    def bench(M, N, K, mode, rot):
+        us = C.c_float()
+        rc = L.nvllm_debug_gemm_bench2(ctx.h, M, N, K, 0, 0, 0, 0, mode, rot, 20, C.byref(us))
+        return us.value if rc == 0 else float("nan")
+
+    for name, (N, K) in SHAPES.items():
+        for M in (1, 16, 64):
+            rot = max(2, int(700e6 / (N * K * 2)))
+            base_mode = 22 if bench(M, N, K, 22, 1) == bench(M, N, K, 22, 1) else 0  # NaN: the streaming kernel does not cover it
+            t8, tb = [], []
+            for _ in range(3):
+                t8.append(bench(M, N, K, 8, rot))
+                tb.append(bench(M, N, K, base_mode, rot))
+            u8, ub = statistics.median(t8), statistics.median(tb)
+            b8 = N * K + (N // 16) * (K // 128) * 4
+            print(f"{name:12s} M={M:3d}  fp8 {u8:7.2f} us {b8 / u8 / 1e6:5.2f} TB/s   bf16 (mode {base_mode:2d}) {ub:7.2f} us "
+                  f"{2 * N * K / ub / 1e6:5.2f} TB/s   fp8/bf16 time {u8 / ub:.2f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
