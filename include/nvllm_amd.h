@@ -118,7 +118,8 @@ int nvllm_model_finalize(nvllm_model* m);
  * tensor: the factor that MULTIPLIES the code, whatever the name suggests), or as f32 / bf16, quantised on load.  An F8
  * tensor offered to a BF16-format model is NVLLM_EINVAL; nvllm_model_finalize is NVLLM_ESTATE when codes lack their scales; a
  * tensor-parallel shard whose first column is not a multiple of 128 is NVLLM_EINVAL (no published Qwen3 shape at tp <= 8).
- * An FP8 model runs the generic forward path at every row count (no epilogue-fused FP8 GEMMs yet). */
+ * An FP8 model runs the generic forward path at every row count.  Prompt chunks (more than 64 rows) run the FP8 tile GEMM,
+ * whose gate/up form has the SwiGLU epilogue; there is no fused QKV epilogue and no epilogue-fused decode GEMM for FP8 yet. */
 int nvllm_model_set_weight_format(nvllm_model* m, int format);
 /* bytes of weights this rank reads per decode step (layers + final norm + LM head; embedding excluded) */
 int64_t nvllm_model_weight_bytes(const nvllm_model* m);

@@ -37,7 +37,8 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
  *       "oneshot_spins": bound of its wait kernel's poll; "oneshot_skip_push": test hook (this rank skips N pushes);
  *   "stream_combine" (default 0): let the fused forward use the streaming GEMM's in-launch split-K combine epilogues (fewer
  *       launches; measured slower on MI355X than slabs + a consumer launch);
- *   "tile_min_wgs" (default 192; 0 never, 1 whenever the shape fits), "tile_fuse_qk" (default 1): the prefill tile GEMM;
+ *   "tile_min_wgs" (default 192; 0 never, 1 whenever the shape fits): the prefill tile GEMM of either weight format;
+ *       "tile_fuse_qk" (default 1): its fused QKV epilogue (bf16 weights only);
  *   "attn_balanced" (0 | 1; from the next step on): the debug spelling of nvllm_model_set_attention_schedule (nvllm_amd.h);
  *   "attn_balanced_wgs" (default 0): spans (workgroups) per kv head of the balanced schedule; 0 = two workgroups per CU over
  *       the local kv heads; positive values are for tests and tuning, clamped to what nvllm_kv_alloc sized the partial
@@ -48,7 +49,7 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
 int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
 
 /* counters for tests: "oneshot_calls" = all-reduces run on the one-shot device path by this model's context;
- * "tile_gemm_launches" = projections run by the prefill tile GEMM; "tile_qkv_fused_launches" = QKV projections among
+ * "tile_gemm_launches" = projections run by the prefill tile GEMM (bf16 or FP8); "tile_qkv_fused_launches" = QKV projections among
  * them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of the LDS-staged
  * prefill attention kernel (one per layer and prompt chunk, whatever the cache width); "attn_balanced_launches" = launches
  * of the work-balanced decode attention kernel (one per layer and decode step that qualifies); "attn_shared_launches" = launches
@@ -79,7 +80,9 @@ int nvllm_debug_gemm_bench(nvllm_ctx* ctx, int M, int N, int K, int nt, int nw, 
                            float* us_per_call);
 
 /* tuning aid v2: explicit m-tiles per workgroup, epilogue mode (0 slabs, 2 SwiGLU with N = 2I) and `rot` weight
- * copies cycled per launch (cold HBM like the model; 1 = cache-warm) */
+ * copies cycled per launch (cold HBM like the model; 1 = cache-warm).  mode 8 = the FP8 weight GEMM, 9 = the FP8 prefill
+ * tile GEMM with slabs (n_split 0 = planner, else exactly), 7 = the same with the SwiGLU epilogue, 1 / 3 = the bf16 tile
+ * GEMM with slabs / the SwiGLU epilogue */
 int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt, int nw, int n_split, int mode, int rot,
                             int iters, float* us_per_call);
 
@@ -94,6 +97,14 @@ int nvllm_debug_gemm_tile_check(nvllm_ctx* ctx, int M, int N, int K, int mode, i
  * N % 16 == 0, K % 128 == 0.  Runs split hi/lo -> pack -> the GEMM, up to two K slices -> slab sum. */
 int nvllm_debug_linear_fp8(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
                            float* y);
+
+/* The FP8 prefill tile GEMM alone (w8_tile_gemm.hip), for its parity test; x, y, codes, scales as nvllm_debug_linear_fp8.
+ * mode 0: y[M][N] = the sum of the K slabs.  mode 2 (SwiGLU epilogue): codes = [2I][K] in checkpoint order, gate rows then
+ * up rows (N = 2I; the entry interleaves them as the loader does); y[M][I] = hi + lo of the planes the kernel wrote, in
+ * row-major (act_packed 0) or fragment order (1).  n_split: 0 = the planner's K split, else exactly that many slices.
+ * NVLLM_EINVAL for a shape or split the kernel does not cover (N % 256, K % 128, n_split must divide K / 128). */
+int nvllm_debug_linear_fp8_tile(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                                int mode, int act_packed, int n_split, float* y);
 
 /* tuning aid: time the decode attention (one new token per sequence, ctx_lens[B] cached tokens each) on a
  * synthetic cache; part_tokens > 0 splits every context into workgroups of that many tokens */

@@ -1634,7 +1634,7 @@ static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, 
     return NVLLM_OK;
 }
 
-// the same for an FP8 projection: one kernel at every row count, as many K slices as fill the chip and fit the slab buffer
+// the same for an FP8 projection off the tile GEMM: one kernel at every row count, as many K slices as fill the chip and fit the slab buffer
 static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW8& w, float* out, int R,
                       int max_split, int* n_slabs) {
     const int fit = (int)std::min<size_t>((size_t)max_split, m->slab_floats / ((size_t)R * w.N));
@@ -1767,25 +1767,30 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     // big-model decode: when all four projections of a layer run the streaming GEMM, the activation planes between
     // the row kernels and the GEMMs stay in MFMA fragment order (xpack_off): x staging costs 3x per byte otherwise
     const bool no_xpack = m->opt_no_xpack != 0;
-    // FP8 projections: row-major planes into the one FP8 GEMM (f32 slabs); every consumer of the slabs is as for bf16
+    // FP8 projections: f32 slabs (every consumer of them is as for bf16) from the one FP8 GEMM on row-major planes, or, on
+    // prompt chunks, from the FP8 tile GEMM (w8_tile_gemm.hip), which also has the SwiGLU epilogue
     const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;
     const int w8_ks = R <= kFusedMaxRows ? 16 : 8;
     const int packed = !fp8 && !no_xpack && !m->layers.empty() && gemm_streams(m, m->layers[0].qkv, R) && gemm_streams(m, m->layers[0].o, R) &&
                        gemm_streams(m, m->layers[0].gu, R) && gemm_streams(m, m->layers[0].down, R) && m->I_l % 32 == 0;
-    // prompt chunks (MFMA-bound): projections whose grid fills the chip run the tile GEMM (tile_gemm.hip); it reads both
-    // operands in fragment order, so the kernel that produces its input planes writes them that way
+    // prompt chunks (MFMA-bound): projections whose grid fills the chip run the tile GEMM (tile_gemm.hip, or
+    // w8_tile_gemm.hip on FP8 codes); it reads both operands in fragment order, so the kernel that produces its input
+    // planes writes them that way
     const int KO = m->nh_l * hd;
     const int tmin = m->opt_tile_min_wgs;
-    const bool tile_on = !fp8 && !packed && tmin > 0 && R > kFusedMaxRows;
+    const bool tile_on = !packed && tmin > 0 && R > kFusedMaxRows;
     // K splits (f32 slabs summed by the consumer): up to 4 on prompt chunks; a few hundred decode rows are MFMA-bound
     // too (hi + lo planes: 4 flops per weight byte and row) and need up to 8 to fill the chip
     const int max_ks = R <= 512 ? 8 : 4;
-    const int o_ks = tile_on ? gemm_tile_splits(R, H, KO, tmin, max_ks) : 0, d_ks = tile_on ? gemm_tile_splits(R, H, m->I_l, tmin, max_ks) : 0;
-    const int q_ks = tile_on ? gemm_tile_splits(R, NQ, H, tmin, max_ks) : 0;
+    auto tile_splits = [&](int N, int K) {
+        return !tile_on ? 0 : fp8 ? gemm_w8_tile_splits(R, N, K, tmin, max_ks) : gemm_tile_splits(R, N, K, tmin, max_ks);
+    };
+    const int o_ks = tile_splits(H, KO), d_ks = tile_splits(H, m->I_l), q_ks = tile_splits(NQ, H);
     const bool t_qkv = q_ks > 0 && (size_t)q_ks * R * NQ <= m->slab_floats;
-    const bool t_qkv_fused = t_qkv && m->opt_tile_fuse_qk && gemm_tile_qkv_ok(R, NQ, H, hd, tmin);
+    // FP8: no fused QKV epilogue; the tile GEMM writes slabs and the row kernel follows, as after the FP8 GEMM
+    const bool t_qkv_fused = !fp8 && t_qkv && m->opt_tile_fuse_qk && gemm_tile_qkv_ok(R, NQ, H, hd, tmin);
     const bool t_o = o_ks > 0 && (size_t)o_ks * R * H <= m->slab_floats;
-    const bool t_gu = tile_on && gemm_tile_ok(R, 2 * m->I_l, H, 2, tmin);
+    const bool t_gu = tile_on && (fp8 ? gemm_w8_tile_ok(R, 2 * m->I_l, H, 2, tmin) : gemm_tile_ok(R, 2 * m->I_l, H, 2, tmin));
     const bool t_down = t_gu && m->I_l % 32 == 0 && d_ks > 0 && (size_t)d_ks * R * H <= m->slab_floats;
     m->tile_launches += (int64_t)m->L * ((int)t_qkv + (int)t_o + (int)t_gu + (int)t_down);
     for (int l = 0; l < m->L; ++l) {
@@ -1815,7 +1820,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
             PROF(m, PROF_GEMM, launch_gemm_tile_qkv(m->xh, m->xl, w.qkv, R, qa, tmin, s));
             ++m->tile_qkv_fused_launches;
         } else {
-            if (t_qkv) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.qkv, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &qa.n_slabs, s));
+            if (t_qkv && fp8) PROF(m, PROF_GEMM, launch_gemm_w8_tile(m->xh, m->xl, w.qkv8, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, 0, &qa.n_slabs, s));
+            else if (t_qkv) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.qkv, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &qa.n_slabs, s));
             else if (fp8) rcg = gemm_slabs(m, m->xh, m->xl, H, w.qkv8, m->slabs, R, w8_ks, &qa.n_slabs);
             else rcg = gemm_slabs(m, m->xh, m->xl, H, w.qkv, m->slabs, R, 8, &qa.n_slabs, packed);
             if (rcg) return rcg;
@@ -1844,7 +1850,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // output projection (qwen3.rs:278) + TP all-reduce
         int o_slabs = 1;
-        if (t_o) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.o, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &o_slabs, s));
+        if (t_o && fp8) PROF(m, PROF_GEMM, launch_gemm_w8_tile(m->xh, m->xl, w.o8, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, 0, &o_slabs, s));
+        else if (t_o) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.o, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &o_slabs, s));
         else if (fp8) rcg = gemm_slabs(m, m->xh, m->xl, KO, w.o8, m->slabs, R, w8_ks, &o_slabs);
         else rcg = gemm_slabs(m, m->xh, m->xl, KO, w.o, m->slabs, R, 8, &o_slabs, packed);
         if (rcg) return rcg;
@@ -1857,7 +1864,9 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         nb.weight = w.ln2; nb.eps = eps; nb.H = H; nb.xh = m->xh; nb.xl = m->xl; nb.out_packed = packed || t_gu;
         PROF(m, PROF_NORM, launch_add_rmsnorm(nb, R, s));
         // MLP (qwen3.rs:323-327)
-        if (t_gu) {
+        if (t_gu && fp8) {
+            PROF(m, PROF_GEMM, launch_gemm_w8_tile(m->xh, m->xl, w.gu8, R, 2, nullptr, m->xh2, m->xl2, t_down ? 1 : 0, tmin, 1, 0, nullptr, s));
+        } else if (t_gu) {
             PROF(m, PROF_GEMM, launch_gemm_tile(m->xh, m->xl, w.gu, R, 2, nullptr, m->xh2, m->xl2, t_down ? 1 : 0, tmin, 1, nullptr, s));
         } else if (fp8) {
             // FP8 gate/up: slabs of the INTERLEAVED gate/up rows, then SiLU*mul on their sum
@@ -1884,7 +1893,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
             PROF(m, PROF_GEMM, launch_gemm_swiglu(pg, m->xh, m->xl, H, w.gu, R, m->xh2, m->xl2, nullptr, s));
         }
         int d_slabs = 1;
-        if (t_down) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh2, m->xl2, w.down, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &d_slabs, s));
+        if (t_down && fp8) PROF(m, PROF_GEMM, launch_gemm_w8_tile(m->xh2, m->xl2, w.down8, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, 0, &d_slabs, s));
+        else if (t_down) PROF(m, PROF_GEMM, launch_gemm_tile(m->xh2, m->xl2, w.down, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, &d_slabs, s));
         else if (fp8) rcg = gemm_slabs(m, m->xh2, m->xl2, m->I_l, w.down8, m->slabs, R, w8_ks, &d_slabs);
         else rcg = gemm_slabs(m, m->xh2, m->xl2, m->I_l, w.down, m->slabs, R, 8, &d_slabs, packed);
         if (rcg) return rcg;
@@ -2616,6 +2626,69 @@ extern "C" int nvllm_debug_linear_fp8(nvllm_ctx* ctx, const float* x, const uint
     return NVLLM_OK;
 }
 
+// the FP8 prefill tile GEMM alone (tests/test_fp8_tile_gpu.py): mode 0 slabs summed into y[M][N]; mode 2 codes = [2I][K]
+// gate rows then up rows, y[M][I] = hi + lo of the SwiGLU planes.  n_split 0 = the planner's K split, else exactly that many.
+extern "C" int nvllm_debug_linear_fp8_tile(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                                           int mode, int act_packed, int n_split, float* y) {
+    if (!ctx || !x || !codes || !scales || !y || (mode != 0 && mode != 2) || n_split < 0 || M < 1 || N < 1 || K < 1)
+        return fail(ctx, NVLLM_EINVAL, "bad linear_fp8_tile arguments");
+    const bool ok = n_split > 0 ? K % 128 == 0 && (K / 128) % n_split == 0 && (mode == 0 || n_split == 1) && gemm_w8_tile_ok(M, N, K, mode, 1)
+                                : gemm_w8_tile_ok(M, N, K, mode, 1);
+    if (!ok) return fail(ctx, NVLLM_EINVAL, "no FP8 tile shape for M=%d N=%d K=%d mode=%d n_split=%d", M, N, K, mode, n_split);
+    for (size_t i = 0; i < (size_t)N * K; ++i)
+        if ((codes[i] & 0x7Fu) == 0x7Fu) return fail(ctx, NVLLM_EINVAL, "NaN code at element %zu", i);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    TmpBufs t;
+    PackedW8 w;
+    w.N = N; w.K = K;
+    const size_t Mp = (size_t)(M + 15) / 16 * 16;
+    const int I = N / 2, KB = K / 128, max_ks = 8;
+    bf16_bits *hi, *lo, *ph, *pl, *ah, *al;
+    uint8_t* dcodes;
+    float* slabs;
+    HIPCHK(ctx, t.get(&w.codes, w.code_bytes() / 16));
+    HIPCHK(ctx, t.get(&w.scales, w.scale_bytes() / 4));
+    HIPCHK(ctx, t.get(&dcodes, (size_t)N * K));
+    HIPCHK(ctx, t.get(&hi, Mp * K)); HIPCHK(ctx, t.get(&lo, Mp * K));
+    HIPCHK(ctx, t.get(&ph, Mp * K)); HIPCHK(ctx, t.get(&pl, Mp * K));
+    HIPCHK(ctx, t.get(&ah, Mp * I)); HIPCHK(ctx, t.get(&al, Mp * I));
+    HIPCHK(ctx, t.get(&slabs, (size_t)std::max(n_split, max_ks) * M * N));
+    HIPCHK(ctx, hipMemcpy(dcodes, codes, (size_t)N * K, hipMemcpyHostToDevice));
+    if (mode == 2) {  // gate rows -> even 16-row tiles, up rows -> odd ones, as the loader places them
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, 0, 0, I, 0, 0));
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, I, 0, I, 0, 1));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, I, dcodes, K, 0, s));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, I, dcodes + (size_t)I * K, K, 1, s));
+    } else {
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, 0, 0, N, 0, -1));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, N, dcodes, K, -1, s));
+    }
+    HIPCHK(ctx, launch_split_hilo_pad(x, M, K, K, hi, lo, s));
+    HIPCHK(ctx, launch_xpack_plane(hi, ph, M, K, s));
+    HIPCHK(ctx, launch_xpack_plane(lo, pl, M, K, s));
+    int ns = 1;
+    HIPCHK(ctx, launch_gemm_w8_tile(ph, pl, w, M, mode, slabs, ah, al, act_packed, 1, max_ks, n_split, mode == 0 ? &ns : nullptr, s));
+    if (mode == 0) {
+        HIPCHK(ctx, launch_slab_sum_ld(slabs, ns, (int64_t)M * N, N, nullptr, M, N, y, N, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return NVLLM_OK;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::vector<uint16_t> h(Mp * I), l(Mp * I);
+    std::vector<float> yh((size_t)M * I);
+    HIPCHK(ctx, hipMemcpy(h.data(), ah, h.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(l.data(), al, l.size() * 2, hipMemcpyDeviceToHost));
+    auto f = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float v; memcpy(&v, &u, 4); return v; };
+    for (int r = 0; r < M; ++r)
+        for (int c = 0; c < I; ++c) {
+            const size_t i = act_packed ? xpack_off(r, c, I >> 5) : (size_t)r * I + c;
+            yh[(size_t)r * I + c] = f(h[i]) + f(l[i]);
+        }
+    HIPCHK(ctx, hipMemcpy(y, yh.data(), yh.size() * 4, hipMemcpyHostToDevice));
+    return NVLLM_OK;
+}
+
 extern "C" int nvllm_op_rmsnorm(nvllm_ctx* ctx, const float* x, const float* residual, const float* weight, double eps,
                                 int rows, int n, float* y, float* residual_out) {
     if (!ctx || !x || !weight || !y || rows < 1 || n < 1) return fail(ctx, NVLLM_EINVAL, "bad rmsnorm arguments");
@@ -2982,6 +3055,8 @@ extern "C" int nvllm_debug_xcc_map(nvllm_ctx* ctx, int gx, int gy, int gz, int t
 // tuning aid, v2: mode 0 = slabs, 2 = SwiGLU epilogue (N = 2I); mt = m-tiles per workgroup (0 = planner);
 // `rot` weight copies are cycled so every launch streams cold HBM like the model does (1 = cache-warm).
 // mode 8 = the FP8 weight GEMM (w8_gemm.hip) on the same matrices quantised per block; n_split = most K slices (0: 16)
+// mode 9 / 7 = the FP8 prefill tile GEMM (w8_tile_gemm.hip) on them, slabs (n_split: 0 planner, else exactly) / SwiGLU epilogue;
+// mode 1 / 3 = the bf16 tile GEMM (tile_gemm.hip), slabs / SwiGLU epilogue -- the x planes are read as fragment order
 extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt, int nw, int n_split, int mode,
                                        int rot, int iters, float* us_per_call) {
     // diagnostic build: mode 22 / 23 + 100 * a = ablation variant a of the streaming kernel (stream_gemm.hip ABL)
@@ -3007,7 +3082,11 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
         HIPCHK(ctx, t.get(&ws[r].data, (size_t)N * K / 8));
         HIPCHK(ctx, launch_synth_packed(ws[r], 0, N, synth_plain(12345 + r, kSynthMatrix), 0, 0, K, -1, s));
     }
-    std::vector<PackedW8> w8s(mode == 8 ? rot : 0);
+    const bool w8_tile = mode == 9 || mode == 7, bf_tile = mode == 1 || mode == 3;
+    if (w8_tile && !gemm_w8_tile_ok(M, N, K, mode == 9 ? 0 : 2, 1)) return fail(ctx, NVLLM_EINVAL, "no FP8 tile shape for M=%d N=%d K=%d", M, N, K);
+    if (mode == 9 && n_split > 0 && ((K / 128) % n_split || n_split > 32)) return fail(ctx, NVLLM_EINVAL, "n_split %d does not divide K / 128", n_split);
+    if (bf_tile && !gemm_tile_ok(M, N, K, mode == 1 ? 0 : 2, 1)) return fail(ctx, NVLLM_EINVAL, "no tile shape for M=%d N=%d K=%d", M, N, K);
+    std::vector<PackedW8> w8s(mode == 8 || w8_tile ? rot : 0);
     for (size_t r = 0; r < w8s.size(); ++r) {
         w8s[r].N = N; w8s[r].K = K;
         HIPCHK(ctx, t.get(&w8s[r].codes, (size_t)N * K / 16));
@@ -3016,9 +3095,11 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
     }
     const int w8_split = std::min(n_split > 0 ? n_split : 16, 32);
     if (mode == 8) p.n_split = 32;  // slab room for any split
+    if (w8_tile || bf_tile) p.n_split = mode == 9 ? std::max(8, n_split) : mode == 1 ? 8 : 1;
     bf16_bits *xh, *xl, *ah, *al; float* out;
-    HIPCHK(ctx, t.get(&xh, (size_t)M * K)); HIPCHK(ctx, t.get(&xl, (size_t)M * K));
-    HIPCHK(ctx, t.get(&ah, (size_t)M * N)); HIPCHK(ctx, t.get(&al, (size_t)M * N));
+    const size_t Mp = (size_t)(M + 15) / 16 * 16;  // the tile kernels read and write whole 16-row tiles of the planes
+    HIPCHK(ctx, t.get(&xh, Mp * K)); HIPCHK(ctx, t.get(&xl, Mp * K));
+    HIPCHK(ctx, t.get(&ah, Mp * N)); HIPCHK(ctx, t.get(&al, Mp * N));
     HIPCHK(ctx, t.get(&out, (size_t)p.n_split * M * N));
     HIPCHK(ctx, launch_synth_rowmajor_bf16(xh, synth_plain(777, kSynthMatrix), 0, (int64_t)M * K, s));
     HIPCHK(ctx, launch_synth_rowmajor_bf16(xl, synth_plain(778, kSynthMatrix), 0, (int64_t)M * K, s));
@@ -3045,6 +3126,10 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
     auto go = [&](int i) -> hipError_t {
         const PackedW& w = ws[i % rot];
         if (mode == 8) { int ns = 1; return launch_gemm_w8(xh, xl, K, w8s[i % rot], out, M, w8_split, &ns, s); }
+        if (mode == 9) { int ns = 1; return launch_gemm_w8_tile(xh, xl, w8s[i % rot], M, 0, out, nullptr, nullptr, 0, 1, 8, n_split, &ns, s); }
+        if (mode == 7) return launch_gemm_w8_tile(xh, xl, w8s[i % rot], M, 2, nullptr, ah, al, 1, 1, 1, 0, nullptr, s);
+        if (mode == 1) { int ns = 1; return launch_gemm_tile(xh, xl, w, M, 0, out, nullptr, nullptr, 0, 1, 8, &ns, s); }
+        if (mode == 3) return launch_gemm_tile(xh, xl, w, M, 2, nullptr, ah, al, 1, 1, 1, nullptr, s);
         if (mode == 20 || mode == 21) return launch_gemm_argmax(plm, xh, xl, K, w, nullptr, M, pv, pi, nullptr, s);
         if (mode == 22 || mode == 23) return launch_gemm_stream(xh, xl, K, w, out, M, mode == 23, s);  // 23: packed x planes
         if (mode >= 10) {

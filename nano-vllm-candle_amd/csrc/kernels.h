@@ -42,6 +42,17 @@ struct PackedW8 {
 bool gemm_w8_ok(int M, int N, int K);
 hipError_t launch_gemm_w8(const bf16_bits* xh, const bf16_bits* xl, int ldx, const PackedW8& w, float* out, int M, int max_split,
                           int* n_slabs, hipStream_t s);
+// The same product on prompt chunks (w8_tile_gemm.hip): 128-row x 256-feature workgroup tiles, x planes in xpack_off order,
+// the codes staged through LDS beside them.  mode 0: f32 slabs out[ks][M][N]; mode 2: w = interleaved gate/up, act hi/lo
+// [M][N/2] (row-major or xpack_off order).  N % 256 == 0, K % 128 == 0; min_wgs as launch_gemm_tile.
+bool gemm_w8_tile_ok(int M, int N, int K, int mode, int min_wgs);
+// K splits mode 0 would use, a divisor of K / 128 (f32 slabs, summed by the consumer); 0 = shape not covered
+int gemm_w8_tile_splits(int M, int N, int K, int min_wgs, int max_split);
+// n_slabs (nullable: never split) = slices written; force_split > 0: exactly that many slices (hipErrorNotSupported when
+// it does not divide K / 128), 0: the planner's choice up to max_split
+hipError_t launch_gemm_w8_tile(const bf16_bits* xh, const bf16_bits* xl, const PackedW8& w, int M, int mode, float* out,
+                               bf16_bits* act_hi, bf16_bits* act_lo, int act_packed, int min_wgs, int max_split, int force_split,
+                               int* n_slabs, hipStream_t s);
 // quantise rows [0, rows) of a bf16 source into rows dst row0.. (ileave as launch_pack_rows): per 128 x 128 block of the
 // SOURCE TENSOR scale = amax / 448 (1 for an all-zero block), code = nearest-even e4m3 of w / scale, saturating.  row_phase =
 // tensor row of source row 0, mod 128 (where the tensor's row blocks start; a shard that begins inside a block quantises

@@ -1,7 +1,9 @@
 """The FP8 weight GEMM (w8_gemm.hip) against the bf16 slab GEMMs on the Qwen3-8B / 32B layer shapes, kernel alone:
 nvllm_debug_gemm_bench2 mode 8 (FP8) against mode 22 (streaming kernel, where it covers the shape) or mode 0 (planner's
 chunked kernel), device events around 20 launches that cycle enough weight copies to stream cold HBM, arms interleaved,
-three rounds; prints the median microseconds and the weight bytes per second of each arm."""
+three rounds; prints the median microseconds and the weight bytes per second of each arm.  Then the prompt-chunk rows
+(512 and 4096): the FP8 prefill tile GEMM (w8_tile_gemm.hip, mode 9; mode 7 = its SwiGLU epilogue on gate_up) against
+mode 8 (what FP8 chunks ran before it) and the bf16 tile GEMM (mode 1 / 3), with the MFMA rate of each arm."""
 import ctypes as C
 import os
 import statistics
@@ -23,8 +25,9 @@ def main():
         rc = L.nvllm_debug_gemm_bench2(ctx.h, M, N, K, 0, 0, 0, 0, mode, rot, 20, C.byref(us))
         return us.value if rc == 0 else float("nan")
 
+    only_chunks = sys.argv[1:] == ["chunks"]  # `ab_w8_gemm.py chunks`: the prompt-chunk rows alone
     for name, (N, K) in SHAPES.items():
-        for M in (1, 16, 64):
+        for M in () if only_chunks else (1, 16, 64):
             rot = max(2, int(700e6 / (N * K * 2)))
             base_mode = 22 if bench(M, N, K, 22, 1) == bench(M, N, K, 22, 1) else 0  # NaN: the streaming kernel does not cover it
             t8, tb = [], []
@@ -35,6 +38,20 @@ def main():
             b8 = N * K + (N // 16) * (K // 128) * 4
             print(f"{name:12s} M={M:3d}  fp8 {u8:7.2f} us {b8 / u8 / 1e6:5.2f} TB/s   bf16 (mode {base_mode:2d}) {ub:7.2f} us "
                   f"{2 * N * K / ub / 1e6:5.2f} TB/s   fp8/bf16 time {u8 / ub:.2f}", flush=True)
+
+    for name, (N, K) in SHAPES.items():
+        gu = name.endswith("gate_up")
+        for M in (512, 4096):
+            rot = max(2, int(700e6 / (N * K * 2)))
+            arms = {"fp8 tile": 7 if gu else 9, "fp8 gemm_w8": 8, "bf16 tile": 3 if gu else 1}
+            t = {a: [] for a in arms}
+            for _ in range(3):
+                for a, mode in arms.items():
+                    t[a].append(bench(M, N, K, mode, rot))
+            u = {a: statistics.median(v) for a, v in t.items()}
+            pf = 4.0 * M * N * K  # hi + lo planes
+            print(f"{name:12s} M={M:4d}  " + "   ".join(f"{a} {u[a]:8.1f} us {pf / u[a] / 1e9:6.1f} PF/s" for a in arms) +
+                  f"   tile/gemm_w8 {u['fp8 tile'] / u['fp8 gemm_w8']:.2f}  tile/bf16 tile {u['fp8 tile'] / u['bf16 tile']:.2f}", flush=True)
 
 
 if __name__ == "__main__":
