@@ -82,7 +82,8 @@ int nvllm_debug_gemm_bench(nvllm_ctx* ctx, int M, int N, int K, int nt, int nw, 
 /* tuning aid v2: explicit m-tiles per workgroup, epilogue mode (0 slabs, 2 SwiGLU with N = 2I) and `rot` weight
  * copies cycled per launch (cold HBM like the model; 1 = cache-warm).  mode 8 = the FP8 weight GEMM, 9 = the FP8 prefill
  * tile GEMM with slabs (n_split 0 = planner, else exactly), 7 = the same with the SwiGLU epilogue, 1 / 3 = the bf16 tile
- * GEMM with slabs / the SwiGLU epilogue */
+ * GEMM with slabs / the SwiGLU epilogue, 10 / 11 / 12 = the row-parallel decode GEMM with epilogue 0 / 1 / 2 (M <= 128),
+ * 30 / 31 / 32 = the FP8 register-direct decode GEMM with the same epilogues */
 int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt, int nw, int n_split, int mode, int rot,
                             int iters, float* us_per_call);
 
@@ -105,6 +106,20 @@ int nvllm_debug_linear_fp8(nvllm_ctx* ctx, const float* x, const uint8_t* codes,
  * NVLLM_EINVAL for a shape or split the kernel does not cover (N % 256, K % 128, n_split must divide K / 128). */
 int nvllm_debug_linear_fp8_tile(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
                                 int mode, int act_packed, int n_split, float* y);
+
+/* The FP8 register-direct decode GEMM alone (w8_rowdir_gemm.hip), for its parity test; x, y, codes, scales as
+ * nvllm_debug_linear_fp8; resid [M][N], next_w [N], row_ssq [M] and every output are DEVICE f32.  x_packed / o_packed: the
+ * kernel reads / writes its hi + lo planes in fragment order (o_packed needs a plane width % 32 == 0).
+ * epi 2: y[M][N] = the complete sums.
+ * epi 1 (SwiGLU): codes = [2I][K] in checkpoint order, gate rows then up rows (N = 2I; the entry interleaves them as the
+ *   loader does); row_ssq (nullable) = a pending norm with one group, rinv[r] = 1 / sqrt(row_ssq[r] / K + 1e-6) scales gate
+ *   and up; y[M][I] = hi + lo of the planes.
+ * epi 0: y[M][N] = resid + sums (the new residual), x_next[M][N] = hi + lo of the planes next_w (.) y, ssq_out[M] = the sum
+ *   of squares of y's rows (the kernel's groups added up).
+ * NVLLM_EINVAL where the kernel has no form for (M, N, K, epi): K in {1024, 2048, 3072, 4096}, M <= 128. */
+int nvllm_debug_linear_fp8_rowdir(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                                  int epi, int x_packed, int o_packed, const float* resid, const float* next_w,
+                                  const float* row_ssq, float* y, float* x_next, float* ssq_out);
 
 /* tuning aid: time the decode attention (one new token per sequence, ctx_lens[B] cached tokens each) on a
  * synthetic cache; part_tokens > 0 splits every context into workgroups of that many tokens */

@@ -105,6 +105,7 @@ _SIGS = {
     "nvllm_debug_gemm_tile_check": (C.c_int, [_vp] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 4),
     "nvllm_debug_linear_fp8": (C.c_int, [_vp, _fp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _fp]),
     "nvllm_debug_linear_fp8_tile": (C.c_int, [_vp, _fp, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [_fp]),
+    "nvllm_debug_linear_fp8_rowdir": (C.c_int, [_vp, _fp, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [_fp] * 6),
     "nvllm_debug_xcc_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nvllm_debug_attn_bench": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "nvllm_dev_alloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
@@ -116,7 +117,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS)
 _DEBUG_EXPORTS_ADDED_LATER = ("nvllm_debug_stamps", "nvllm_debug_stamps_read", "nvllm_ctx_create_null_comm", "nvllm_debug_set_option",
                               "nvllm_debug_gemm_tile_check", "nvllm_debug_get_counter", "nvllm_model_set_attention_schedule",
                               "nvllm_decode_next_sample", "nvllm_decode_enqueue_sample", "nvllm_model_set_weight_format",
-                              "nvllm_debug_linear_fp8", "nvllm_debug_linear_fp8_tile")
+                              "nvllm_debug_linear_fp8", "nvllm_debug_linear_fp8_tile", "nvllm_debug_linear_fp8_rowdir")
 
 _lib = None
 

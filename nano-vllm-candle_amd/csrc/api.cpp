@@ -546,6 +546,7 @@ struct nvllm_model {
     bool stamps_on = false;
     int stamp_launch = 0;
     int64_t tile_launches = 0;  // projections run by the tile GEMM so far (tests assert the path they force was taken)
+    int64_t w8_rowdir_launches = 0;  // projections run by the FP8 register-direct GEMM (the fused path of an FP8 model)
     int64_t tile_qkv_fused_launches = 0;  // ... QKV projections among them with the fused norm + RoPE + KV-write epilogue
     int64_t attn_prefill_launches = 0;    // launches of the LDS-staged prefill attention kernel
 
@@ -1375,7 +1376,18 @@ static bool fused_plan(const nvllm_model* m, int R, FusedPlan& p) {
     const int H = m->H, hd = m->hd, NQ = (m->nh_l + 2 * m->kv_l) * hd, KO = m->nh_l * hd, I2 = 2 * m->I_l;
     const bool tp = m->ctx->tp_size > 1;
     if (R > kFusedMaxRows || m->taps || m->opt_no_fused) return false;
-    if (m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128) return false;  // FP8 projections: f32 slabs only (no epilogue-fused forms yet)
+    const bool no_xpack = m->opt_no_xpack != 0;
+    if (m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128) {
+        // FP8 projections: all four on the FP8 register-direct kernel (w8_rowdir_gemm.hip) or the generic path -- there is
+        // no FP8 form of the streaming epilogues, and a mixed layer would pay the slab round trips it is here to remove
+        const int er = tp ? 2 : 0;
+        if (!(gemm_rowdir_w8_ok(NQ, H, 2, R) && gemm_rowdir_w8_ok(H, KO, er, R) && gemm_rowdir_w8_ok(I2, H, 1, R) &&
+              gemm_rowdir_w8_ok(H, m->I_l, er, R)))
+            return false;
+        p.qkv = p.o = p.gu = p.down = G_ROW;
+        p.packed = !no_xpack && R >= 16 && m->I_l % 32 == 0;
+        return true;
+    }
     auto fits = [&](int N, int K, int epi) {
         return m->opt_stream_combine && gemm_stream_ok(R, N, K, epi) && gemm_stream_slab_floats(R, N, K, epi) <= m->slab_floats;
     };
@@ -1404,7 +1416,6 @@ static bool fused_plan(const nvllm_model* m, int R, FusedPlan& p) {
     else if (fits(I2, H, 2)) p.gu = G_STREAM;
     else if (gemm_stream_splits(R, I2, H) > 0) return false;  // big gate/up: streaming slabs + SiLU launch beat the unsplit generic kernel
     else p.gu = G_GENERIC;  // generic kernel with the SwiGLU epilogue (no K split)
-    const bool no_xpack = m->opt_no_xpack != 0;
     auto takes_packed = [&](int kind, int N, int K, int epi) { return kind == G_STREAM || (kind == G_ROW && gemm_rowdir_ok(N, K, epi, R)); };
     // fewer than 16 rows: a fragment-order plane is 15/16 padding (a 1-row step would load 1 KiB per k-tile where a
     // row-major plane serves 64 bytes to all 16 lanes): batch 1 measured 960 -> 1017 tokens/s with row-major planes
@@ -1438,6 +1449,13 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
     const int KO = m->nh_l * hd;
     const bool tp = ctx->tp_size > 1;
     const int packed = fp.packed;
+    const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;  // fused_plan: every projection is G_ROW then
+    // a G_ROW projection: the register-direct / row-parallel kernel on the bf16 matrix, or the FP8 register-direct kernel
+    auto row_gemm = [&](const RowParArgs& ra, const PackedW& w, const PackedW8& w8, int epi) -> int {
+        if (fp8) { PROF(m, PROF_GEMM, launch_gemm_rowdir_w8(ra, w8, epi, s)); ++m->w8_rowdir_launches; }
+        else PROF(m, PROF_GEMM, launch_gemm_rowpar(ra, w, epi, s));
+        return NVLLM_OK;
+    };
     m->tap_rows = R;
     m->stamp_launch = 0;
     RowNorm rn;  // the norm pending on xh/xl
@@ -1459,8 +1477,8 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         return NVLLM_OK;
     };
     // row-parallel projection (o_proj, down_proj) of input planes (xh_, xl_) [R, K]: tp = 1 epilogue or partial + all-reduce + prep
-    auto row_linear = [&](int kind, const PackedW& w, const bf16_bits* xh_, const bf16_bits* xl_, int K, const float* next_w,
-                          float* ssq_buf, int o_packed) -> int {
+    auto row_linear = [&](int kind, const PackedW& w, const PackedW8& w8, const bf16_bits* xh_, const bf16_bits* xl_, int K,
+                          const float* next_w, float* ssq_buf, int o_packed) -> int {
         if (!tp) {
             if (kind == G_ROW) {
                 RowParArgs ra;
@@ -1468,8 +1486,8 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
                 ra.oh = m->xh; ra.ol = m->xl; ra.ssq = ssq_buf; ra.ssq_stride = kFusedMaxRows; ra.M = R;
                 ra.x_packed = packed; ra.o_packed = o_packed;
                 STAMPS(ra, m);
-                PROF(m, PROF_GEMM, launch_gemm_rowpar(ra, w, 0, s));
-                rn.ssq = ssq_buf; rn.groups = gemm_rowpar_groups(H, K);
+                if (int rc = row_gemm(ra, w, w8, 0)) return rc;
+                rn.ssq = ssq_buf; rn.groups = fp8 ? gemm_rowdir_w8_groups(H, K) : gemm_rowpar_groups(H, K);
             } else {
                 StreamArgs sa = stream_args(xh_, xl_, K);
                 sa.resid_in = m->resid; sa.resid_out = m->resid; sa.next_w = next_w; sa.oh = m->xh; sa.ol = m->xl; sa.o_packed = o_packed;
@@ -1482,7 +1500,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         if (kind == G_ROW) {
             RowParArgs ra;
             ra.xh = xh_; ra.xl = xl_; ra.ldx = K; ra.out = m->red; ra.M = R; ra.x_packed = packed;
-            PROF(m, PROF_GEMM, launch_gemm_rowpar(ra, w, 2, s));
+            if (int rc = row_gemm(ra, w, w8, 2)) return rc;
         } else if (kind == G_STREAM) {
             StreamArgs sa = stream_args(xh_, xl_, K);
             sa.out = m->red;
@@ -1518,7 +1536,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
             RowParArgs rq;
             rq.xh = m->xh; rq.xl = m->xl; rq.ldx = H; rq.out = m->slabs; rq.M = R; rq.x_packed = packed;
             STAMPS(rq, m);
-            PROF(m, PROF_GEMM, launch_gemm_rowpar(rq, w.qkv, 2, s));
+            if (int rc = row_gemm(rq, w.qkv, w.qkv8, 2)) return rc;
             qa.qkv = m->slabs;
         } else if (fp.qkv == G_STREAM) {
             StreamArgs sa = stream_args(m->xh, m->xl, H);
@@ -1563,7 +1581,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         else if (m->shp_on) { PROF(m, PROF_ATTN, launch_attn_shared(aa, m->shp, R, s)); ++m->attn_shared_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
         // o_proj (+ residual + post-attention norm prep; qwen3.rs:278, :393)
-        int rc = row_linear(fp.o, w.o, m->ctxh, m->ctxl, KO, w.ln2, m->ssqA, packed);
+        int rc = row_linear(fp.o, w.o, w.o8, m->ctxh, m->ctxl, KO, w.ln2, m->ssqA, packed);
         if (rc) return rc;
         // gate/up + SiLU*mul (qwen3.rs:324-325), scaled by the pending norm's rinv
         if (fp.gu == G_ROW) {
@@ -1571,7 +1589,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
             rg.xh = m->xh; rg.xl = m->xl; rg.ldx = H; rg.oh = m->xh2; rg.ol = m->xl2; rg.M = R; rg.rn = rn;
             rg.x_packed = packed; rg.o_packed = packed;
             STAMPS(rg, m);
-            PROF(m, PROF_GEMM, launch_gemm_rowpar(rg, w.gu, 1, s));
+            if (int rc2 = row_gemm(rg, w.gu, w.gu8, 1)) return rc2;
         } else if (fp.gu == G_STREAM) {
             StreamArgs sa = stream_args(m->xh, m->xl, H);
             sa.rn = rn; sa.oh = m->xh2; sa.ol = m->xl2; sa.o_packed = packed;
@@ -1582,7 +1600,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         }
         // down_proj (+ residual + next layer's input norm prep; qwen3.rs:326, next layer :378; last layer: final norm :497)
         const bool last = l + 1 == m->L;
-        rc = row_linear(fp.down, w.down, m->xh2, m->xl2, m->I_l, last ? m->norm : m->layers[l + 1].ln1, m->ssqB,
+        rc = row_linear(fp.down, w.down, w.down8, m->xh2, m->xl2, m->I_l, last ? m->norm : m->layers[l + 1].ln1, m->ssqB,
                         packed && !last);  // the LM head (chunked kernel) reads row-major planes
         if (rc) return rc;
     }
@@ -2441,7 +2459,8 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
 // "tile_gemm_launches" = projections this model has run on the prefill tile GEMM; "tile_qkv_fused_launches" = QKV
 // projections among them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of
 // the LDS-staged prefill attention kernel; "attn_balanced_launches" = launches of the work-balanced decode attention kernel;
-// "attn_shared_launches" = launches of the shared-prefix decode attention kernel
+// "attn_shared_launches" = launches of the shared-prefix decode attention kernel; "w8_rowdir_launches" = projections run by
+// the FP8 register-direct GEMM (four per layer of every fused chunk of an FP8 model)
 extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value) {
     if (!m || !name || !value) return NVLLM_EINVAL;
     if (!strcmp(name, "oneshot_calls")) { *value = (int64_t)m->ctx->os_calls; return NVLLM_OK; }
@@ -2450,6 +2469,7 @@ extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t
     if (!strcmp(name, "attn_prefill_launches")) { *value = m->attn_prefill_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_balanced_launches")) { *value = m->attn_balanced_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_shared_launches")) { *value = m->attn_shared_launches; return NVLLM_OK; }
+    if (!strcmp(name, "w8_rowdir_launches")) { *value = m->w8_rowdir_launches; return NVLLM_OK; }
     if (!strcmp(name, "kv_f16_saturated") || !strcmp(name, "kv_f16_absmax_bits")) {
         // scan of the whole K/V pool (debug, off the hot path): elements the f16_sat clamp of a cache write produced, and the
         // largest magnitude stored (f16 bits; 0x7BFF = 65504 is the clamp)
@@ -2686,6 +2706,78 @@ extern "C" int nvllm_debug_linear_fp8_tile(nvllm_ctx* ctx, const float* x, const
             yh[(size_t)r * I + c] = f(h[i]) + f(l[i]);
         }
     HIPCHK(ctx, hipMemcpy(y, yh.data(), yh.size() * 4, hipMemcpyHostToDevice));
+    return NVLLM_OK;
+}
+
+// the FP8 register-direct decode GEMM alone with each of its epilogues (tests/test_fp8_rowdir_gpu.py); see nvllm_amd_debug.h
+extern "C" int nvllm_debug_linear_fp8_rowdir(nvllm_ctx* ctx, const float* x, const uint8_t* codes, const float* scales, int M, int N, int K,
+                                             int epi, int x_packed, int o_packed, const float* resid, const float* next_w,
+                                             const float* row_ssq, float* y, float* x_next, float* ssq_out) {
+    if (!ctx || !x || !codes || !scales || !y || M < 1 || N < 1 || K < 1 || epi < 0 || epi > 2 ||
+        (epi == 0 && (!resid || !next_w || !x_next || !ssq_out)))
+        return fail(ctx, NVLLM_EINVAL, "bad linear_fp8_rowdir arguments");
+    const int No = epi == 1 ? N / 2 : N;  // width of the planes
+    if (!gemm_rowdir_w8_ok(N, K, epi, M) || (o_packed && (epi == 2 || No % 32)))
+        return fail(ctx, NVLLM_EINVAL, "no FP8 register-direct shape for M=%d N=%d K=%d epi=%d o_packed=%d", M, N, K, epi, o_packed);
+    for (size_t i = 0; i < (size_t)N * K; ++i)
+        if ((codes[i] & 0x7Fu) == 0x7Fu) return fail(ctx, NVLLM_EINVAL, "NaN code at element %zu", i);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    TmpBufs t;
+    PackedW8 w;
+    w.N = N; w.K = K;
+    const size_t Mp = (size_t)(M + 15) / 16 * 16;
+    const int KB = K / 128, groups = gemm_rowdir_w8_groups(N, K);
+    bf16_bits *hi, *lo, *ph, *pl, *oh, *ol;
+    uint8_t* dcodes;
+    float* ssq;
+    HIPCHK(ctx, t.get(&w.codes, w.code_bytes() / 16));
+    HIPCHK(ctx, t.get(&w.scales, w.scale_bytes() / 4));
+    HIPCHK(ctx, t.get(&dcodes, (size_t)N * K));
+    HIPCHK(ctx, t.get(&hi, Mp * K)); HIPCHK(ctx, t.get(&lo, Mp * K));
+    HIPCHK(ctx, t.get(&ph, Mp * K)); HIPCHK(ctx, t.get(&pl, Mp * K));
+    HIPCHK(ctx, t.get(&oh, Mp * No)); HIPCHK(ctx, t.get(&ol, Mp * No));
+    HIPCHK(ctx, t.get(&ssq, (size_t)std::max(groups, 1) * M));
+    HIPCHK(ctx, hipMemcpy(dcodes, codes, (size_t)N * K, hipMemcpyHostToDevice));
+    if (epi == 1) {  // gate rows -> even 16-row tiles, up rows -> odd ones, as the loader places them
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, 0, 0, No, 0, 0));
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, No, 0, No, 0, 1));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, No, dcodes, K, 0, s));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, No, dcodes + (size_t)No * K, K, 1, s));
+    } else {
+        HIPCHK(ctx, upload_w8_scales(w, scales, KB, 0, 0, N, 0, -1));
+        HIPCHK(ctx, launch_pack_codes_w8(w, 0, N, dcodes, K, -1, s));
+    }
+    HIPCHK(ctx, launch_split_hilo_pad(x, M, K, K, hi, lo, s));
+    if (x_packed) {
+        HIPCHK(ctx, launch_xpack_plane(hi, ph, M, K, s));
+        HIPCHK(ctx, launch_xpack_plane(lo, pl, M, K, s));
+    }
+    RowParArgs ra;
+    ra.xh = x_packed ? ph : hi; ra.xl = x_packed ? pl : lo; ra.ldx = K; ra.M = M; ra.x_packed = x_packed; ra.o_packed = o_packed;
+    ra.resid_in = resid; ra.resid_out = y; ra.next_w = next_w; ra.oh = oh; ra.ol = ol; ra.ssq = ssq; ra.ssq_stride = M; ra.out = y;
+    if (row_ssq) { ra.rn.ssq = row_ssq; ra.rn.groups = 1; ra.rn.stride = M; ra.rn.inv_h = 1.0f / (float)K; ra.rn.eps = 1e-6f; }
+    HIPCHK(ctx, launch_gemm_rowdir_w8(ra, w, epi, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (epi == 2) return NVLLM_OK;
+    std::vector<uint16_t> h(Mp * No), l(Mp * No);
+    std::vector<float> planes((size_t)M * No);
+    HIPCHK(ctx, hipMemcpy(h.data(), oh, h.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(l.data(), ol, l.size() * 2, hipMemcpyDeviceToHost));
+    auto f = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float v; memcpy(&v, &u, 4); return v; };
+    for (int r = 0; r < M; ++r)
+        for (int c = 0; c < No; ++c) {
+            const size_t i = o_packed ? xpack_off(r, c, No >> 5) : (size_t)r * No + c;
+            planes[(size_t)r * No + c] = f(h[i]) + f(l[i]);
+        }
+    HIPCHK(ctx, hipMemcpy(epi == 1 ? y : x_next, planes.data(), planes.size() * 4, hipMemcpyHostToDevice));
+    if (epi == 0) {
+        std::vector<float> g((size_t)groups * M), tot(M, 0.f);
+        HIPCHK(ctx, hipMemcpy(g.data(), ssq, g.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 0; k < groups; ++k)
+            for (int r = 0; r < M; ++r) tot[r] += g[(size_t)k * M + r];
+        HIPCHK(ctx, hipMemcpy(ssq_out, tot.data(), tot.size() * 4, hipMemcpyHostToDevice));
+    }
     return NVLLM_OK;
 }
 
@@ -3057,6 +3149,7 @@ extern "C" int nvllm_debug_xcc_map(nvllm_ctx* ctx, int gx, int gy, int gz, int t
 // mode 8 = the FP8 weight GEMM (w8_gemm.hip) on the same matrices quantised per block; n_split = most K slices (0: 16)
 // mode 9 / 7 = the FP8 prefill tile GEMM (w8_tile_gemm.hip) on them, slabs (n_split: 0 planner, else exactly) / SwiGLU epilogue;
 // mode 1 / 3 = the bf16 tile GEMM (tile_gemm.hip), slabs / SwiGLU epilogue -- the x planes are read as fragment order
+// mode 30 / 31 / 32 = the FP8 register-direct decode GEMM (w8_rowdir_gemm.hip) with epilogue 0 / 1 / 2, as modes 10..12
 extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int mt, int nt, int nw, int n_split, int mode,
                                        int rot, int iters, float* us_per_call) {
     // diagnostic build: mode 22 / 23 + 100 * a = ablation variant a of the streaming kernel (stream_gemm.hip ABL)
@@ -3086,7 +3179,9 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
     if (w8_tile && !gemm_w8_tile_ok(M, N, K, mode == 9 ? 0 : 2, 1)) return fail(ctx, NVLLM_EINVAL, "no FP8 tile shape for M=%d N=%d K=%d", M, N, K);
     if (mode == 9 && n_split > 0 && ((K / 128) % n_split || n_split > 32)) return fail(ctx, NVLLM_EINVAL, "n_split %d does not divide K / 128", n_split);
     if (bf_tile && !gemm_tile_ok(M, N, K, mode == 1 ? 0 : 2, 1)) return fail(ctx, NVLLM_EINVAL, "no tile shape for M=%d N=%d K=%d", M, N, K);
-    std::vector<PackedW8> w8s(mode == 8 || w8_tile ? rot : 0);
+    const bool w8_rowdir = mode >= 30 && mode <= 32;
+    if (w8_rowdir && !gemm_rowdir_w8_ok(N, K, mode - 30, M)) return fail(ctx, NVLLM_EINVAL, "no FP8 register-direct shape for N=%d K=%d epi=%d", N, K, mode - 30);
+    std::vector<PackedW8> w8s(mode == 8 || w8_tile || w8_rowdir ? rot : 0);
     for (size_t r = 0; r < w8s.size(); ++r) {
         w8s[r].N = N; w8s[r].K = K;
         HIPCHK(ctx, t.get(&w8s[r].codes, (size_t)N * K / 16));
@@ -3109,8 +3204,8 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
         if (!gemm_stream_splits(M, N, K)) return fail(ctx, NVLLM_EINVAL, "no streaming shape for M=%d N=%d K=%d", M, N, K);
         float* o2; HIPCHK(ctx, t.get(&o2, (size_t)gemm_stream_splits(M, N, K) * M * N)); out = o2;
     }
-    if (mode >= 10 && mode < 20) {
-        if (!gemm_rowpar_ok(N, K, mode - 10, M)) return fail(ctx, NVLLM_EINVAL, "no row-parallel shape for N=%d K=%d epi=%d", N, K, mode - 10);
+    if ((mode >= 10 && mode < 20) || w8_rowdir) {
+        if (!w8_rowdir && !gemm_rowpar_ok(N, K, mode - 10, M)) return fail(ctx, NVLLM_EINVAL, "no row-parallel shape for N=%d K=%d epi=%d", N, K, mode - 10);
         HIPCHK(ctx, t.get(&resid, (size_t)M * N)); HIPCHK(ctx, t.get(&nextw, (size_t)N));
         HIPCHK(ctx, t.get(&ssq, (size_t)1024 * 128)); HIPCHK(ctx, t.get(&ssq_in, (size_t)128));
         HIPCHK(ctx, hipMemsetAsync(resid, 0, (size_t)M * N * 4, s)); HIPCHK(ctx, hipMemsetAsync(nextw, 0, (size_t)N * 4, s));
@@ -3133,10 +3228,12 @@ extern "C" int nvllm_debug_gemm_bench2(nvllm_ctx* ctx, int M, int N, int K, int 
         if (mode == 20 || mode == 21) return launch_gemm_argmax(plm, xh, xl, K, w, nullptr, M, pv, pi, nullptr, s);
         if (mode == 22 || mode == 23) return launch_gemm_stream(xh, xl, K, w, out, M, mode == 23, s);  // 23: packed x planes
         if (mode >= 10) {
+            if (mode >= 33) return hipErrorInvalidValue;
             RowParArgs ra;
             ra.xh = xh; ra.xl = xl; ra.ldx = K; ra.M = M; ra.out = out; ra.resid_in = resid; ra.resid_out = resid; ra.next_w = nextw;
             ra.oh = ah; ra.ol = al; ra.ssq = ssq; ra.ssq_stride = 128;
             ra.rn.ssq = ssq_in; ra.rn.groups = 1; ra.rn.stride = 128; ra.rn.inv_h = 1.0f / K; ra.rn.eps = 1e-6f;
+            if (w8_rowdir) return launch_gemm_rowdir_w8(ra, w8s[i % rot], mode - 30, s);
             return launch_gemm_rowpar(ra, w, mode - 10, s);
         }
         return mode == 2 ? launch_gemm_swiglu(p, xh, xl, K, w, M, ah, al, nullptr, s) : launch_gemm(p, xh, xl, K, w, out, M, s);

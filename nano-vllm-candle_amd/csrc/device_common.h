@@ -24,6 +24,17 @@ __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) 
     hi = __builtin_bit_cast(uint16_t, h);
     lo = __builtin_bit_cast(uint16_t, (__bf16)(x - (float)h));
 }
+// FP8 weights (PackedW8): one 8-code half of a lane slot -> one bf16 A-fragment, no lane movement.  The conversion is exact
+// (every finite e4m3 number is a bf16 number); the converter's scale operand stays 1.0 -- block scales are applied in f32.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ bf16x8 w8_frag(uint32_t d0, uint32_t d1) {
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false);
+    const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false);
+    const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
+    return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1, 2, 3,
+                                   4, 5, 6, 7);
+}
 __device__ __forceinline__ _Float16 f16_sat(float x) { return (_Float16)fminf(fmaxf(x, -65504.f), 65504.f); }
 
 // 24-bit V (opt-in): beside the f16 value the cache keeps the rounding residual r = x - f16(x) as the TOP BYTE

@@ -415,6 +415,18 @@ int gemm_rowpar_splits(int N, int K, int epi, int M);  // f32 slabs the plain ep
 int gemm_rowpar_groups(int N, int K);
 // epi: 0 residual + next-norm prep, 1 SwiGLU, 2 plain f32 output
 hipError_t launch_gemm_rowpar(const RowParArgs& a, const PackedW& w, int epi, hipStream_t s);
+// shape of the register-direct kernel for (N, K, epi, M): nt n-tiles per workgroup, nwk waves, tk k-tiles per wave; nt == 0:
+// not applicable.  elem_bytes = bytes per weight element streamed (2 bf16, 1 FP8 codes): the big-matrix cut-off is in bytes
+struct RowDirShape { int nt, nwk, tk; };
+RowDirShape rowdir_shape(int N, int K, int epi, int M, int elem_bytes);
+
+// ---- the same on block-scaled FP8 weights (w8_rowdir_gemm.hip) ---------------------------------------------------
+// The register-direct kernel reading PackedW8 as it is: a wave's weight set is half the loads, the codes become bf16
+// fragments in registers, each 64-column partial sum takes its block scale in f32 before the LDS reduction.  Epilogues,
+// RowParArgs fields and packed planes as launch_gemm_rowpar's register-direct form; K in {1024, 2048, 3072, 4096}.
+bool gemm_rowdir_w8_ok(int N, int K, int epi, int M);
+int gemm_rowdir_w8_groups(int N, int K);  // ssq groups epilogue 0 leaves
+hipError_t launch_gemm_rowdir_w8(const RowParArgs& a, const PackedW8& w, int epi, hipStream_t s);
 
 // ---- SwiGLU -----------------------------------------------------------------------------------------
 // gu [n_slabs][rows][2*I] -> act hi/lo [rows][I] (and/or f32 y)

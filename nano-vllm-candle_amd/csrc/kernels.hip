@@ -1419,9 +1419,7 @@ __global__ void __launch_bounds__(NWK * 64) gemm_rowdir_kernel(RowParArgs a, con
     NVLLM_STAMP(a, 4);
 }
 
-// shape of the register-direct kernel for (N, K, epi, M): nt == 0 -> not applicable
-struct RowDirShape { int nt, nwk, tk; };
-static RowDirShape rowdir_shape(int N, int K, int epi, int M) {
+RowDirShape rowdir_shape(int N, int K, int epi, int M, int elem_bytes) {
     RowDirShape none{0, 0, 0};
     if (N % 16 || K % 32 || M > 128) return none;
     const int KT = K / 32, ntiles = N / 16;
@@ -1445,7 +1443,7 @@ static RowDirShape rowdir_shape(int N, int K, int epi, int M) {
         if (M <= 16 && ntiles <= 512) nt = 1;  // as above (0.6B QKV: 64 -> 256 workgroups)
     }
     // weights are streamed once per row block: big matrices belong to the 64-row kernel
-    if ((size_t)N * K * 2 >= ((size_t)24 << 20) && M > 16) return none;
+    if ((size_t)N * K * elem_bytes >= ((size_t)24 << 20) && M > 16) return none;
     return RowDirShape{nt, 16, tk};
 }
 
@@ -1488,24 +1486,24 @@ static bool rowpar_shape(int N, int K, int epi, int M, RowParShape& sh) {
 }
 bool gemm_rowpar_supported(int N, int K) {
     RowParShape sh;
-    return (rowdir_shape(N, K, 0, 64).nt || rowpar_shape(N, K, 0, 64, sh)) && gemm_rowpar_groups(N, K) <= 64;
+    return (rowdir_shape(N, K, 0, 64, 2).nt || rowpar_shape(N, K, 0, 64, sh)) && gemm_rowpar_groups(N, K) <= 64;
 }
 bool gemm_rowpar_ok(int N, int K, int epi, int M) {
-    if (rowdir_shape(N, K, epi, M).nt) return true;
+    if (rowdir_shape(N, K, epi, M, 2).nt) return true;
     RowParShape sh;
     return rowpar_shape(N, K, epi, M, sh) && !(epi == 1 && sh.nwn % 2);
 }
 // ssq groups the epilogue-0 kernel leaves (independent of M: the fused path never exceeds 128 rows)
 int gemm_rowpar_groups(int N, int K) {
-    const RowDirShape d = rowdir_shape(N, K, 0, 64);
+    const RowDirShape d = rowdir_shape(N, K, 0, 64, 2);
     if (d.nt) return (N / 16 + d.nt - 1) / d.nt;
     RowParShape sh;
     if (!rowpar_shape(N, K, 0, 64, sh)) return 0;
     return (N / 16 + sh.nwn - 1) / sh.nwn;
 }
-bool gemm_rowdir_ok(int N, int K, int epi, int M) { return rowdir_shape(N, K, epi, M).nt != 0; }
+bool gemm_rowdir_ok(int N, int K, int epi, int M) { return rowdir_shape(N, K, epi, M, 2).nt != 0; }
 int gemm_rowpar_splits(int N, int K, int epi, int M) {
-    if (rowdir_shape(N, K, epi, M).nt) return 1;
+    if (rowdir_shape(N, K, epi, M, 2).nt) return 1;
     RowParShape sh;
     return rowpar_shape(N, K, epi, M, sh) ? sh.ns : 0;
 }
@@ -1560,7 +1558,7 @@ static hipError_t rowpar_dispatch(const RowParShape& sh, const RowParArgs& a, co
 }
 
 hipError_t launch_gemm_rowpar(const RowParArgs& a, const PackedW& w, int epi, hipStream_t s) {
-    if (const RowDirShape d = rowdir_shape(w.N, w.K, epi, a.M); d.nt) {
+    if (const RowDirShape d = rowdir_shape(w.N, w.K, epi, a.M, 2); d.nt) {
         if (a.M <= 0) return hipSuccess;
         if (epi == 0) return rowdir_dispatch<0>(d, a, w, s);
         if (epi == 1) return rowdir_dispatch<1>(d, a, w, s);

@@ -16,18 +16,6 @@
 
 namespace nvllm {
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-// one 8-code half of a lane slot -> one bf16 A-fragment, no lane movement
-__device__ __forceinline__ bf16x8 w8_frag(uint32_t d0, uint32_t d1) {
-    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false);
-    const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
-    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false);
-    const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
-    return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1, 2, 3,
-                                   4, 5, 6, 7);
-}
-
 // ---------------------------------------------------------------------------------------------------
 // out[ks][M][N] = x[M][K-slice ks] . (s (.) q)[N][K-slice ks]^T, f32 slabs.
 // One workgroup = 8 waves = 8*NT n-tiles x MT*16 rows x one K slice (a whole number of 128-column blocks).  A wave owns NT

@@ -3,7 +3,9 @@ nvllm_debug_gemm_bench2 mode 8 (FP8) against mode 22 (streaming kernel, where it
 chunked kernel), device events around 20 launches that cycle enough weight copies to stream cold HBM, arms interleaved,
 three rounds; prints the median microseconds and the weight bytes per second of each arm.  Then the prompt-chunk rows
 (512 and 4096): the FP8 prefill tile GEMM (w8_tile_gemm.hip, mode 9; mode 7 = its SwiGLU epilogue on gate_up) against
-mode 8 (what FP8 chunks ran before it) and the bf16 tile GEMM (mode 1 / 3), with the MFMA rate of each arm."""
+mode 8 (what FP8 chunks ran before it) and the bf16 tile GEMM (mode 1 / 3), with the MFMA rate of each arm.
+`rowdir`: instead, the FP8 register-direct decode GEMM (w8_rowdir_gemm.hip, mode 30 + epilogue) against the bf16
+gemm_rowdir_kernel (mode 10 + epilogue) and gemm_w8_kernel (mode 8) at the four Qwen3-0.6B layer shapes, 1 / 16 / 64 rows."""
 import ctypes as C
 import os
 import statistics
@@ -25,6 +27,21 @@ def main():
         rc = L.nvllm_debug_gemm_bench2(ctx.h, M, N, K, 0, 0, 0, 0, mode, rot, 20, C.byref(us))
         return us.value if rc == 0 else float("nan")
 
+    if sys.argv[1:] == ["rowdir"]:  # `ab_w8_gemm.py rowdir`: the fused decode path's GEMMs at the Qwen3-0.6B layer shapes
+        # the FP8 register-direct kernel (mode 30 + epilogue) against its bf16 twin (10 + epilogue) and the FP8 slab GEMM (8)
+        layer = {"0.6B qkv": (4096, 1024, 2), "0.6B o": (1024, 2048, 0), "0.6B gate_up": (6144, 1024, 1), "0.6B down": (1024, 3072, 0)}
+        for name, (N, K, epi) in layer.items():
+            for M in (1, 16, 64):
+                rot = max(2, int(700e6 / (N * K * 2)))
+                arms = {"fp8 rowdir": 30 + epi, "bf16 rowdir": 10 + epi, "fp8 gemm_w8": 8}
+                t = {a: [] for a in arms}
+                for _ in range(3):
+                    for a, mode in arms.items():
+                        t[a].append(bench(M, N, K, mode, rot))
+                u = {a: statistics.median(v) for a, v in t.items()}
+                print(f"{name:12s} epi {epi} M={M:3d}  " + "   ".join(f"{a} {u[a]:6.2f} us" for a in arms) +
+                      f"   fp8/bf16 rowdir {u['fp8 rowdir'] / u['bf16 rowdir']:.2f}  rowdir/gemm_w8 {u['fp8 rowdir'] / u['fp8 gemm_w8']:.2f}", flush=True)
+        return
     only_chunks = sys.argv[1:] == ["chunks"]  # `ab_w8_gemm.py chunks`: the prompt-chunk rows alone
     for name, (N, K) in SHAPES.items():
         for M in () if only_chunks else (1, 16, 64):
