@@ -119,7 +119,8 @@ int nvllm_model_finalize(nvllm_model* m);
  * tensor offered to a BF16-format model is NVLLM_EINVAL; nvllm_model_finalize is NVLLM_ESTATE when codes lack their scales; a
  * tensor-parallel shard whose first column is not a multiple of 128 is NVLLM_EINVAL (no published Qwen3 shape at tp <= 8).
  * An FP8 model runs the generic forward path at every row count.  Prompt chunks (more than 64 rows) run the FP8 tile GEMM,
- * whose gate/up form has the SwiGLU epilogue; there is no fused QKV epilogue and no epilogue-fused decode GEMM for FP8 yet. */
+ * whose gate/up form has the SwiGLU epilogue and whose QKV form (head_dim 128, an even number of local q + k + v heads) has
+ * the fused q/k-norm + RoPE + KV-write epilogue of the bf16 tile GEMM, for every K/V cache width. */
 int nvllm_model_set_weight_format(nvllm_model* m, int format);
 /* bytes of weights this rank reads per decode step (layers + final norm + LM head; embedding excluded) */
 int64_t nvllm_model_weight_bytes(const nvllm_model* m);

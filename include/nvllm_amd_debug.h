@@ -38,7 +38,7 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
  *   "stream_combine" (default 0): let the fused forward use the streaming GEMM's in-launch split-K combine epilogues (fewer
  *       launches; measured slower on MI355X than slabs + a consumer launch);
  *   "tile_min_wgs" (default 192; 0 never, 1 whenever the shape fits): the prefill tile GEMM of either weight format;
- *       "tile_fuse_qk" (default 1): its fused QKV epilogue (bf16 weights only);
+ *       "tile_fuse_qk" (default 1): its fused QKV epilogue (bf16, or FP8: gemm_w8_tile_qkv_kernel);
  *   "attn_balanced" (0 | 1; from the next step on): the debug spelling of nvllm_model_set_attention_schedule (nvllm_amd.h);
  *   "attn_balanced_wgs" (default 0): spans (workgroups) per kv head of the balanced schedule; 0 = two workgroups per CU over
  *       the local kv heads; positive values are for tests and tuning, clamped to what nvllm_kv_alloc sized the partial

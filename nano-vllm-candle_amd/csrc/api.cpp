@@ -1805,8 +1805,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     };
     const int o_ks = tile_splits(H, KO), d_ks = tile_splits(H, m->I_l), q_ks = tile_splits(NQ, H);
     const bool t_qkv = q_ks > 0 && (size_t)q_ks * R * NQ <= m->slab_floats;
-    // FP8: no fused QKV epilogue; the tile GEMM writes slabs and the row kernel follows, as after the FP8 GEMM
-    const bool t_qkv_fused = !fp8 && t_qkv && m->opt_tile_fuse_qk && gemm_tile_qkv_ok(R, NQ, H, hd, tmin);
+    // fused QKV epilogue (q/k-norm + RoPE + KV write): tile_gemm.hip modes 3..5, or w8_tile_qkv_gemm.hip on FP8 codes
+    const bool t_qkv_fused = t_qkv && m->opt_tile_fuse_qk && (fp8 ? gemm_w8_tile_qkv_ok(R, NQ, H, hd, tmin) : gemm_tile_qkv_ok(R, NQ, H, hd, tmin));
     const bool t_o = o_ks > 0 && (size_t)o_ks * R * H <= m->slab_floats;
     const bool t_gu = tile_on && (fp8 ? gemm_w8_tile_ok(R, 2 * m->I_l, H, 2, tmin) : gemm_tile_ok(R, 2 * m->I_l, H, 2, tmin));
     const bool t_down = t_gu && m->I_l % 32 == 0 && d_ks > 0 && (size_t)d_ks * R * H <= m->slab_floats;
@@ -1834,8 +1834,10 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         const bool fuse_qk = qt == 1 && n_tiles == R && !m->shp_on;  // decode: every q-tile is one row (the shared-prefix kernel reads qbuf)
         int rcg = NVLLM_OK;
         if (t_qkv_fused && !fuse_qk) {
-            // prompt chunk: q/k-norm + RoPE + KV write + q output in the QKV GEMM's epilogue (one wave tile = one head)
-            PROF(m, PROF_GEMM, launch_gemm_tile_qkv(m->xh, m->xl, w.qkv, R, qa, tmin, s));
+            // prompt chunk: q/k-norm + RoPE + KV write + q output in the QKV GEMM's epilogue (a head is one wave tile of the
+            // bf16 kernel, a wave pair's two tiles of the FP8 one)
+            if (fp8) PROF(m, PROF_GEMM, launch_gemm_w8_tile_qkv(m->xh, m->xl, w.qkv8, R, qa, tmin, s));
+            else PROF(m, PROF_GEMM, launch_gemm_tile_qkv(m->xh, m->xl, w.qkv, R, qa, tmin, s));
             ++m->tile_qkv_fused_launches;
         } else {
             if (t_qkv && fp8) PROF(m, PROF_GEMM, launch_gemm_w8_tile(m->xh, m->xl, w.qkv8, R, 0, m->slabs, nullptr, nullptr, 0, tmin, max_ks, 0, &qa.n_slabs, s));

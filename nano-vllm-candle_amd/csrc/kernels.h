@@ -262,6 +262,13 @@ hipError_t launch_gemm_tile(const bf16_bits* xh, const bf16_bits* xl, const Pack
 bool gemm_tile_qkv_ok(int M, int N, int K, int hd, int min_wgs);
 hipError_t launch_gemm_tile_qkv(const bf16_bits* xh, const bf16_bits* xl, const PackedW& w, int M, const QkvArgs& qa, int min_wgs,
                                 hipStream_t s);
+// the same for block-scaled FP8 weights (w8_tile_qkv_gemm.hip): the arithmetic of launch_gemm_w8_tile with one K slice, the
+// epilogue of launch_gemm_tile_qkv.  N % 256 == 0 (an even number of heads), K % 128 == 0, head_dim 128, a pending norm
+// with one group, and a shape whose slab form would not split K (one slice has to fill the chip); hipErrorNotSupported
+// otherwise, hipErrorInvalidValue for 24-bit K without 24-bit V.  qa.qkv is ignored.
+bool gemm_w8_tile_qkv_ok(int M, int N, int K, int hd, int min_wgs);
+hipError_t launch_gemm_w8_tile_qkv(const bf16_bits* xh, const bf16_bits* xl, const PackedW8& w, int M, const QkvArgs& qa, int min_wgs,
+                                   hipStream_t s);
 #ifdef NVLLM_STAMPS
 void tile_gemm_stamps_arm(unsigned long long* base, int max_launches);  // diagnostic build
 int tile_gemm_stamps_count();
