@@ -140,6 +140,12 @@ int nvllm_kv_num_free_blocks(const nvllm_model* m);
  * byte holding its rounding residual (13..14 significant bits, cache bytes x1.5), which every attention kernel -- prefill,
  * decode, the fused QKV epilogue -- reads and writes natively.  24-bit V is what holds the 1e-3 logits bar on
  * heavy-tailed checkpoints; 24-bit K comes only together with 24-bit V; both need head_dim 128 (every Qwen3 size).
+ * (8, 8) is the 8-bit cache: every (token, kv head) row of K and of V is stored as 128 OCP e4m3fn codes plus one f32 scale
+ * (amax / 448), 132 bytes instead of 256 -- 512 / 264 times the tokens per pool byte, about half the K/V bytes a decode
+ * step reads, at e4m3's precision (3 mantissa bits per stored element; q, scores and probabilities keep theirs).  It has an
+ * attention kernel of its own (prompt chunks and decode, split-KV included); K and V are written by the row kernel, so the
+ * fused decode prologue, the fused QKV tile epilogues and the balanced / shared-prefix schedules do not apply to such a
+ * pool (a step runs the default schedule).  8 goes with 8 only, and needs head_dim 128.
  * Takes effect at the next nvllm_kv_alloc.  NVLLM_EINVAL at once for any other combination. */
 int nvllm_model_set_kv_cache_bits(nvllm_model* m, int k_bits, int v_bits);
 /* How the decode attention kernel's work is split over workgroups.  NVLLM_ATTN_PER_SEQUENCE (the default): one workgroup
@@ -253,7 +259,7 @@ int nvllm_op_rope(nvllm_ctx* ctx, float* q, float* k, int B, int nh, int kv, int
  * cache and runs the same paged kernel the step path uses. */
 int nvllm_op_attention(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
                        int T, int hd, float scale, float* out);
-/* ... with the scratch cache k_bits / v_bits wide (16 or 24 each, the combinations nvllm_model_set_kv_cache_bits takes) */
+/* ... with the scratch cache k_bits / v_bits wide (16 or 24 each, or 8 and 8: the combinations nvllm_model_set_kv_cache_bits takes) */
 int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
                           int T, int hd, float scale, int k_bits, int v_bits, float* out);
 

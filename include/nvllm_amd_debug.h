@@ -32,6 +32,8 @@ int nvllm_profile_read(nvllm_model* m, double* total_ms, int64_t* launches);
  *   "kv_v_bits" (16 | 24; takes effect at the next nvllm_kv_alloc): 24 keeps V as f16 + a bf8 residual byte (13..14 bits;
  *       V bytes x1.5; head_dim 128 only) -- the knob for holding the 1e-3 logits bar on heavy-tailed checkpoints;
  *   "kv_k_bits" (16 | 24; at the next nvllm_kv_alloc, which refuses it without "kv_v_bits" = 24): the same for K;
+ *       8 for both selects the 8-bit cache (e4m3 codes + one f32 scale per token and kv head); nvllm_kv_alloc refuses a pair
+ *       with one 8 in it, and keeps the pool it had;
  *       (both kept for A/B runs: a deployment sets the widths with nvllm_model_set_kv_cache_bits, nvllm_amd.h)
  *   "oneshot_allreduce" (0 | 1; at the next nvllm_kv_alloc, every rank alike): one-shot all-reduce for decode messages;
  *       "oneshot_spins": bound of its wait kernel's poll; "oneshot_skip_push": test hook (this rank skips N pushes);
@@ -51,7 +53,8 @@ int nvllm_debug_set_option(nvllm_model* m, const char* name, int value);
 /* counters for tests: "oneshot_calls" = all-reduces run on the one-shot device path by this model's context;
  * "tile_gemm_launches" = projections run by the prefill tile GEMM (bf16 or FP8); "tile_qkv_fused_launches" = QKV projections among
  * them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of the LDS-staged
- * prefill attention kernel (one per layer and prompt chunk, whatever the cache width); "attn_balanced_launches" = launches
+ * prefill attention kernel (one per layer and prompt chunk of a 16- or 24-bit pool); "attn_kv8_launches" = launches of the
+ * 8-bit-cache attention kernel (one per layer and chunk or decode step of an 8-bit pool); "attn_balanced_launches" = launches
  * of the work-balanced decode attention kernel (one per layer and decode step that qualifies); "attn_shared_launches" = launches
  * of the shared-prefix decode attention kernel (one per layer and decode step in which forked sequences share a block); "kv_f16_saturated" = elements of the K/V pool at the
  * f16 clamp (every cache write saturates at +-65504; a scan of the pool, off the hot path); "kv_f16_absmax_bits" = the

@@ -80,9 +80,15 @@ static int fail(nvllm_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-// K/V cache widths: 16 or 24 bits each; 24-bit K only beside 24-bit V; the 24-bit kernels are head_dim 128 (every Qwen3 size)
+// K/V cache widths: 16 or 24 bits each, or 8 bits both (e4m3 codes + one f32 scale per token and kv head, attn_kv8.hip);
+// 24-bit K only beside 24-bit V; the 8- and 24-bit kernels are head_dim 128 (every Qwen3 size)
 static int check_kv_cache_bits(nvllm_ctx* ctx, int k_bits, int v_bits, int hd) {
-    if ((k_bits != 16 && k_bits != 24) || (v_bits != 16 && v_bits != 24)) return fail(ctx, NVLLM_EINVAL, "K/V cache bits are 16 or 24");
+    if (k_bits == 8 || v_bits == 8) {
+        if (k_bits != v_bits) return fail(ctx, NVLLM_EINVAL, "an 8-bit K/V cache is 8 bits for K and V alike (have %d, %d)", k_bits, v_bits);
+        if (hd != 128) return fail(ctx, NVLLM_EINVAL, "the 8-bit K/V cache needs head_dim 128 (have %d)", hd);
+        return NVLLM_OK;
+    }
+    if ((k_bits != 16 && k_bits != 24) || (v_bits != 16 && v_bits != 24)) return fail(ctx, NVLLM_EINVAL, "K/V cache bits are 8 (both), 16 or 24");
     if (k_bits == 24 && v_bits != 24) return fail(ctx, NVLLM_EINVAL, "a 24-bit K cache needs a 24-bit V cache as well");
     if (v_bits == 24 && hd != 128) return fail(ctx, NVLLM_EINVAL, "the 24-bit K/V cache needs head_dim 128 (have %d)", hd);
     return NVLLM_OK;
@@ -455,6 +461,10 @@ struct nvllm_model {
     std::vector<f16_bits*> kcache, vcache;
     std::vector<uint8_t*> vlocache;  // 24-bit V (opt_kv_v_bits == 24): one residual byte per V element, else empty
     std::vector<uint8_t*> klocache;  // 24-bit K (opt_kv_k_bits == 24, only with 24-bit V): the same for K
+    // 8-bit pool (opt_kv_k_bits == opt_kv_v_bits == 8): e4m3 code planes and f32 scale planes per layer (KvLayout::k8 ..);
+    // kcache / vcache then hold null pointers
+    std::vector<uint8_t*> k8cache, v8cache;
+    std::vector<float*> kscache, vscache;
     std::vector<int> free_blocks, free_slots;
     std::unordered_map<int64_t, SeqState> seqs;
     int* d_block_tables = nullptr;
@@ -549,6 +559,7 @@ struct nvllm_model {
     int64_t w8_rowdir_launches = 0;  // projections run by the FP8 register-direct GEMM (the fused path of an FP8 model)
     int64_t tile_qkv_fused_launches = 0;  // ... QKV projections among them with the fused norm + RoPE + KV-write epilogue
     int64_t attn_prefill_launches = 0;    // launches of the LDS-staged prefill attention kernel
+    int64_t attn_kv8_launches = 0;        // launches of the 8-bit-cache attention kernel (either form)
 
     // per-kernel-class HIP-event timing (bench roofline leg); 0 = off
     int prof_kind = 0;
@@ -659,7 +670,12 @@ static void free_kv(nvllm_model* m) {
     for (auto p : m->vcache) (void)hipFree(p);
     for (auto p : m->vlocache) (void)hipFree(p);
     for (auto p : m->klocache) (void)hipFree(p);
+    for (auto p : m->k8cache) (void)hipFree(p);
+    for (auto p : m->v8cache) (void)hipFree(p);
+    for (auto p : m->kscache) (void)hipFree(p);
+    for (auto p : m->vscache) (void)hipFree(p);
     m->kcache.clear(); m->vcache.clear(); m->vlocache.clear(); m->klocache.clear();
+    m->k8cache.clear(); m->v8cache.clear(); m->kscache.clear(); m->vscache.clear();
     void* ptrs[] = {m->d_block_tables, m->d_ids, m->d_pos, m->d_slot, m->d_tile_row0, m->d_tile_nrows, m->d_tile_slot,
                     m->d_last_rows, m->d_tile_order, m->d_tile_last, m->d_group_order, m->resid, m->slabs, m->qbuf, m->logits, m->d_maxval, m->red, m->xh, m->xl, m->xh2, m->xl2, m->ctxh, m->ctxl, m->ssqA, m->ssqB, m->d_next,
                     m->part_val, m->part_idx, m->argmax_scratch, m->attn_po, m->attn_pml, m->bal.plan, m->bal.tickets, m->bal.part_o, m->bal.part_ml, m->tap_h, m->tap_res, m->cosv, m->sinv, m->tickets, m->qkv_out, m->d_keys, m->d_temps, m->d_samp_temps, m->d_samp_base, m->part_sval, m->part_sidx,
@@ -1066,6 +1082,11 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
     nvllm_ctx* ctx = m->ctx;
     if (block_size != kBlockTokens) return fail(ctx, NVLLM_EINVAL, "block_size must be %d (src/engine/sequence.rs:35)", kBlockTokens);
     if (num_blocks < 1 || max_seqs < 1 || max_batched_tokens < 1) return fail(ctx, NVLLM_EINVAL, "non-positive pool sizes");
+    // the debug options set one width at a time: a pair with one 8 in it is refused here, before the old pool is freed
+    if (m->opt_kv_k_bits == 8 || m->opt_kv_v_bits == 8) {
+        const int rcb = check_kv_cache_bits(ctx, m->opt_kv_k_bits, m->opt_kv_v_bits, m->hd);
+        if (rcb) return rcb;
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     free_kv(m);
@@ -1096,7 +1117,25 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
     m->vcache.assign(m->L, nullptr);
     if (m->opt_kv_v_bits == 24) m->vlocache.assign(m->L, nullptr);
     if (m->opt_kv_k_bits == 24) m->klocache.assign(m->L, nullptr);
-    for (int l = 0; l < m->L; ++l) {
+    const bool kv8 = m->opt_kv_k_bits == 8;
+    if (kv8) {
+        // 8-bit pool: code planes of one byte per element, scale planes [num_blocks][kv_l][256] f32, all zero (a scale stays 0
+        // until its token is written; zero codes are the value 0)
+        const size_t scales = (size_t)num_blocks * m->kv_l * kBlockTokens;
+        m->k8cache.assign(m->L, nullptr); m->v8cache.assign(m->L, nullptr);
+        m->kscache.assign(m->L, nullptr); m->vscache.assign(m->L, nullptr);
+        for (int l = 0; l < m->L; ++l) {
+            HIPCHK(ctx, hipMalloc((void**)&m->k8cache[l], per_layer));
+            HIPCHK(ctx, hipMalloc((void**)&m->v8cache[l], per_layer));
+            HIPCHK(ctx, hipMalloc((void**)&m->kscache[l], scales * 4));
+            HIPCHK(ctx, hipMalloc((void**)&m->vscache[l], scales * 4));
+            HIPCHK(ctx, hipMemsetAsync(m->k8cache[l], 0, per_layer, ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(m->v8cache[l], 0, per_layer, ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(m->kscache[l], 0, scales * 4, ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(m->vscache[l], 0, scales * 4, ctx->stream));
+        }
+    }
+    for (int l = 0; l < m->L && !kv8; ++l) {
         HIPCHK(ctx, hipMalloc((void**)&m->kcache[l], per_layer * 2));
         HIPCHK(ctx, hipMalloc((void**)&m->vcache[l], per_layer * 2));
         if (!m->vlocache.empty()) {
@@ -1222,6 +1261,7 @@ extern "C" int nvllm_kv_alloc(nvllm_model* m, int num_blocks, int block_size, in
 extern "C" int nvllm_kv_num_free_blocks(const nvllm_model* m) { return m ? (int)m->free_blocks.size() : 0; }
 extern "C" int64_t nvllm_kv_bytes_per_token(const nvllm_model* m) {
     if (!m) return 0;
+    if (!m->k8cache.empty()) return (int64_t)m->kv_l * (m->hd + 4) * 2 * m->L;  // 8-bit: codes + one f32 scale per row, K and V
     const int64_t v_bytes = m->vlocache.empty() ? 2 : 3;  // 24-bit V: + one residual byte per element
     const int64_t k_bytes = m->klocache.empty() ? 2 : 3;
     return (int64_t)m->kv_l * m->hd * (k_bytes + v_bytes) * m->L;
@@ -1273,7 +1313,14 @@ extern "C" int nvllm_seq_fork(nvllm_model* m, int64_t src_seq_id, int64_t dst_se
     for (int b = n_shared; b < n_blocks; ++b) {
         const int from = src.blocks[b], to = m->free_blocks[m->free_blocks.size() - 1 - (size_t)(b - n_shared)];
         d.blocks.push_back(to);
-        for (int l = 0; l < m->L && e == hipSuccess; ++l) {
+        const size_t blk_rows = (size_t)m->kv_l * kBlockTokens;  // 8-bit pool: the codes AND the scales of the block
+        for (int l = 0; l < m->L && e == hipSuccess && !m->k8cache.empty(); ++l) {
+            e = hipMemcpyAsync(m->k8cache[l] + to * blk_elems, m->k8cache[l] + from * blk_elems, blk_elems, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(m->v8cache[l] + to * blk_elems, m->v8cache[l] + from * blk_elems, blk_elems, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(m->kscache[l] + to * blk_rows, m->kscache[l] + from * blk_rows, blk_rows * 4, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(m->vscache[l] + to * blk_rows, m->vscache[l] + from * blk_rows, blk_rows * 4, hipMemcpyDeviceToDevice, ctx->stream);
+        }
+        for (int l = 0; l < m->L && e == hipSuccess && m->k8cache.empty(); ++l) {
             e = hipMemcpyAsync(m->kcache[l] + to * blk_elems, m->kcache[l] + from * blk_elems, blk_elems * 2, hipMemcpyDeviceToDevice, ctx->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(m->vcache[l] + to * blk_elems, m->vcache[l] + from * blk_elems, blk_elems * 2, hipMemcpyDeviceToDevice, ctx->stream);
             if (e == hipSuccess && !m->vlocache.empty())
@@ -1450,6 +1497,7 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
     const bool tp = ctx->tp_size > 1;
     const int packed = fp.packed;
     const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;  // fused_plan: every projection is G_ROW then
+    const bool kv8 = !m->k8cache.empty();  // 8-bit pool: the step runs as under no_attn_prologue, on the kernel of attn_kv8.hip
     // a G_ROW projection: the register-direct / row-parallel kernel on the bf16 matrix, or the FP8 register-direct kernel
     auto row_gemm = [&](const RowParArgs& ra, const PackedW& w, const PackedW8& w8, int epi) -> int {
         if (fp8) { PROF(m, PROF_GEMM, launch_gemm_rowdir_w8(ra, w8, epi, s)); ++m->w8_rowdir_launches; }
@@ -1556,7 +1604,9 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         qa.kv.k = m->kcache[l]; qa.kv.v = m->vcache[l]; qa.kv.kv_l = m->kv_l; qa.kv.hd = hd;
         qa.kv.vlo = m->vlocache.empty() ? nullptr : m->vlocache[l];
         qa.kv.klo = m->klocache.empty() ? nullptr : m->klocache[l];
-        const bool fuse_qk = qt == 1 && n_tiles == R && !m->opt_no_attn_prologue && !m->shp_on;  // the shared-prefix kernel reads qbuf
+        if (kv8) { qa.kv.k8 = m->k8cache[l]; qa.kv.v8 = m->v8cache[l]; qa.kv.ks = m->kscache[l]; qa.kv.vs = m->vscache[l]; }
+        // the shared-prefix kernel and the 8-bit-cache kernel read qbuf (the row kernel is the 8-bit pool's writer)
+        const bool fuse_qk = qt == 1 && n_tiles == R && !m->opt_no_attn_prologue && !m->shp_on && !kv8;
         if (!fuse_qk) PROF(m, PROF_QK, launch_qk_norm_rope_kvwrite(qa, R, s));
         AttnArgs aa;
         aa.q = m->qbuf; aa.kv = qa.kv; aa.block_tables = m->d_block_tables; aa.max_blocks = m->max_blocks;
@@ -1576,7 +1626,8 @@ static int forward_chunk_fused(nvllm_model* m, const FusedPlan& fp, int R, int n
         }
         PROF(m, PROF_EMPTY, hipSuccess);  // calibration: an event pair around nothing, at the attention launch's place
         STAMPS(aa, m);
-        if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
+        if (kv8) { PROF(m, PROF_ATTN, launch_attn_kv8(aa, n_tiles, qt, R, parts_max, s)); ++m->attn_kv8_launches; }
+        else if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
         else if (m->shp_on) { PROF(m, PROF_ATTN, launch_attn_shared(aa, m->shp, R, s)); ++m->attn_shared_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
@@ -1664,7 +1715,8 @@ static int gemm_slabs(nvllm_model* m, const bf16_bits* xh, const bf16_bits* xl, 
 // Balanced schedule: does this chunk qualify, and if so put its plan on the device -- once, ahead of the layers.  The plan
 // is a function of the positions already there (uploaded, or advanced by launch_advance_decode): no host round trip.
 static int plan_attn_balanced(nvllm_model* m, int R, int n_tiles, int qt) {
-    m->bal_on = m->opt_attn_schedule == NVLLM_ATTN_BALANCED && qt == 1 && n_tiles == R && R <= m->bal.max_rows && m->hd == 128 &&
+    // (an 8-bit pool runs the default schedule of its own kernel)
+    m->bal_on = m->opt_attn_schedule == NVLLM_ATTN_BALANCED && m->k8cache.empty() && qt == 1 && n_tiles == R && R <= m->bal.max_rows && m->hd == 128 &&
                 !m->opt_no_attn_prologue;
     if (!m->bal_on) return NVLLM_OK;
     m->bal_spans = std::min(m->bal.max_spans, m->opt_attn_balanced_wgs > 0 ? m->opt_attn_balanced_wgs : m->bal_auto_spans);
@@ -1678,7 +1730,7 @@ static int plan_attn_balanced(nvllm_model* m, int R, int n_tiles, int qt) {
 static int plan_attn_shared(nvllm_model* m, int R, int n_tiles, int qt) {
     nvllm_ctx* ctx = m->ctx;
     m->shp_on = false;
-    if (m->opt_attn_schedule != NVLLM_ATTN_SHARED_PREFIX || qt != 1 || n_tiles != R || R > m->max_seqs || R > kFusedMaxRows || m->hd != 128 ||
+    if (m->opt_attn_schedule != NVLLM_ATTN_SHARED_PREFIX || !m->k8cache.empty() || qt != 1 || n_tiles != R || R > m->max_seqs || R > kFusedMaxRows || m->hd != 128 ||
         (int)m->row_slot_h.size() != R)
         return NVLLM_OK;
     if (m->shp_valid) { m->shp_on = m->shp.n_shared > 0; return NVLLM_OK; }
@@ -1788,6 +1840,7 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     // FP8 projections: f32 slabs (every consumer of them is as for bf16) from the one FP8 GEMM on row-major planes, or, on
     // prompt chunks, from the FP8 tile GEMM (w8_tile_gemm.hip), which also has the SwiGLU epilogue
     const bool fp8 = m->weight_format == NVLLM_WEIGHTS_FP8_BLOCK128;
+    const bool kv8 = !m->k8cache.empty();
     const int w8_ks = R <= kFusedMaxRows ? 16 : 8;
     const int packed = !fp8 && !no_xpack && !m->layers.empty() && gemm_streams(m, m->layers[0].qkv, R) && gemm_streams(m, m->layers[0].o, R) &&
                        gemm_streams(m, m->layers[0].gu, R) && gemm_streams(m, m->layers[0].down, R) && m->I_l % 32 == 0;
@@ -1806,7 +1859,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
     const int o_ks = tile_splits(H, KO), d_ks = tile_splits(H, m->I_l), q_ks = tile_splits(NQ, H);
     const bool t_qkv = q_ks > 0 && (size_t)q_ks * R * NQ <= m->slab_floats;
     // fused QKV epilogue (q/k-norm + RoPE + KV write): tile_gemm.hip modes 3..5, or w8_tile_qkv_gemm.hip on FP8 codes
-    const bool t_qkv_fused = t_qkv && m->opt_tile_fuse_qk && (fp8 ? gemm_w8_tile_qkv_ok(R, NQ, H, hd, tmin) : gemm_tile_qkv_ok(R, NQ, H, hd, tmin));
+    // (not on an 8-bit pool: its writer is the row kernel, so the tile GEMMs run their slab form)
+    const bool t_qkv_fused = t_qkv && !kv8 && m->opt_tile_fuse_qk && (fp8 ? gemm_w8_tile_qkv_ok(R, NQ, H, hd, tmin) : gemm_tile_qkv_ok(R, NQ, H, hd, tmin));
     const bool t_o = o_ks > 0 && (size_t)o_ks * R * H <= m->slab_floats;
     const bool t_gu = tile_on && (fp8 ? gemm_w8_tile_ok(R, 2 * m->I_l, H, 2, tmin) : gemm_tile_ok(R, 2 * m->I_l, H, 2, tmin));
     const bool t_down = t_gu && m->I_l % 32 == 0 && d_ks > 0 && (size_t)d_ks * R * H <= m->slab_floats;
@@ -1831,7 +1885,9 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
         qa.kv.k = m->kcache[l]; qa.kv.v = m->vcache[l]; qa.kv.kv_l = m->kv_l; qa.kv.hd = hd;
         qa.kv.vlo = m->vlocache.empty() ? nullptr : m->vlocache[l];
         qa.kv.klo = m->klocache.empty() ? nullptr : m->klocache[l];
-        const bool fuse_qk = qt == 1 && n_tiles == R && !m->shp_on;  // decode: every q-tile is one row (the shared-prefix kernel reads qbuf)
+        if (kv8) { qa.kv.k8 = m->k8cache[l]; qa.kv.v8 = m->v8cache[l]; qa.kv.ks = m->kscache[l]; qa.kv.vs = m->vscache[l]; }
+        // decode: every q-tile is one row (the shared-prefix kernel and the 8-bit-cache kernel read qbuf)
+        const bool fuse_qk = qt == 1 && n_tiles == R && !m->shp_on && !kv8;
         int rcg = NVLLM_OK;
         if (t_qkv_fused && !fuse_qk) {
             // prompt chunk: q/k-norm + RoPE + KV write + q output in the QKV GEMM's epilogue (a head is one wave tile of the
@@ -1864,7 +1920,8 @@ static int forward_chunk(nvllm_model* m, int R, int n_tiles, int qt, int n_last,
             parts_max = m->attn_parts_max;
         }
         STAMPS(aa, m);
-        if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
+        if (kv8) { PROF(m, PROF_ATTN, launch_attn_kv8(aa, n_tiles, qt, R, parts_max, s)); ++m->attn_kv8_launches; }
+        else if (qt == 2) { PROF(m, PROF_ATTN, launch_attn_prefill(aa, n_tiles, s)); ++m->attn_prefill_launches; }
         else if (m->bal_on) { PROF(m, PROF_ATTN, launch_attn_balanced(aa, m->bal, R, m->bal_spans, s)); ++m->attn_balanced_launches; }
         else if (m->shp_on) { PROF(m, PROF_ATTN, launch_attn_shared(aa, m->shp, R, s)); ++m->attn_shared_launches; }
         else PROF(m, PROF_ATTN, launch_attn_paged(aa, n_tiles, qt, R, parts_max, s));
@@ -1978,6 +2035,7 @@ static void set_attn_split(nvllm_model* m, int n_seqs, int max_len) {
     // less than the combine launch and its boundary (4.7 + 1.4 us, batch-1 profile)
     if (tiles <= 16) want = 1;
     int part = std::max(4, (tiles + want - 1) / want);  // >= 128 tokens per workgroup
+    if (!m->k8cache.empty()) part = (part + kAttnKv8TileSteps - 1) / kAttnKv8TileSteps * kAttnKv8TileSteps;  // whole 64-token steps
     m->attn_part_tiles = part;
     m->attn_parts_max = (tiles + part - 1) / part;
 }
@@ -2437,13 +2495,14 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
     if (!strcmp(name, "stream_combine")) { m->opt_stream_combine = value; return NVLLM_OK; }
     if (!strcmp(name, "oneshot_allreduce")) { m->opt_oneshot_allreduce = value; return NVLLM_OK; }  // takes effect at the next kv_alloc
     if (!strcmp(name, "oneshot_spins")) { m->opt_oneshot_spins = std::max(1, value); return NVLLM_OK; }
-    // kv_k_bits / kv_v_bits: the debug spelling of nvllm_model_set_kv_cache_bits (nvllm_amd.h), one width at a time
+    // kv_k_bits / kv_v_bits: the debug spelling of nvllm_model_set_kv_cache_bits (nvllm_amd.h), one width at a time (8 needs
+    // both: the pair is checked at kv_alloc)
     if (!strcmp(name, "kv_k_bits")) {  // takes effect at the next kv_alloc (which insists on kv_v_bits = 24 with it)
-        if (value != 16 && value != 24) return fail(m->ctx, NVLLM_EINVAL, "kv_k_bits is 16 or 24");
+        if (value != 8 && value != 16 && value != 24) return fail(m->ctx, NVLLM_EINVAL, "kv_k_bits is 8, 16 or 24");
         m->opt_kv_k_bits = value; return NVLLM_OK;
     }
     if (!strcmp(name, "kv_v_bits")) {  // takes effect at the next kv_alloc
-        if (value != 16 && value != 24) return fail(m->ctx, NVLLM_EINVAL, "kv_v_bits is 16 or 24");
+        if (value != 8 && value != 16 && value != 24) return fail(m->ctx, NVLLM_EINVAL, "kv_v_bits is 8, 16 or 24");
         m->opt_kv_v_bits = value; return NVLLM_OK;
     }
     if (!strcmp(name, "oneshot_skip_push")) { m->opt_oneshot_skip_push = std::max(0, value); return NVLLM_OK; }  // test hook
@@ -2460,7 +2519,8 @@ extern "C" int nvllm_debug_set_option(nvllm_model* m, const char* name, int valu
 // counters for tests: "oneshot_calls" = all-reduces this model's context has run on the one-shot device path;
 // "tile_gemm_launches" = projections this model has run on the prefill tile GEMM; "tile_qkv_fused_launches" = QKV
 // projections among them that ran the fused q/k-norm + RoPE + KV-write epilogue; "attn_prefill_launches" = launches of
-// the LDS-staged prefill attention kernel; "attn_balanced_launches" = launches of the work-balanced decode attention kernel;
+// the LDS-staged prefill attention kernel; "attn_kv8_launches" = launches of the 8-bit-cache attention kernel (prompt chunks
+// and decode steps of an 8-bit pool); "attn_balanced_launches" = launches of the work-balanced decode attention kernel;
 // "attn_shared_launches" = launches of the shared-prefix decode attention kernel; "w8_rowdir_launches" = projections run by
 // the FP8 register-direct GEMM (four per layer of every fused chunk of an FP8 model)
 extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t* value) {
@@ -2469,6 +2529,7 @@ extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t
     if (!strcmp(name, "tile_gemm_launches")) { *value = m->tile_launches; return NVLLM_OK; }
     if (!strcmp(name, "tile_qkv_fused_launches")) { *value = m->tile_qkv_fused_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_prefill_launches")) { *value = m->attn_prefill_launches; return NVLLM_OK; }
+    if (!strcmp(name, "attn_kv8_launches")) { *value = m->attn_kv8_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_balanced_launches")) { *value = m->attn_balanced_launches; return NVLLM_OK; }
     if (!strcmp(name, "attn_shared_launches")) { *value = m->attn_shared_launches; return NVLLM_OK; }
     if (!strcmp(name, "w8_rowdir_launches")) { *value = m->w8_rowdir_launches; return NVLLM_OK; }
@@ -2476,6 +2537,7 @@ extern "C" int nvllm_debug_get_counter(nvllm_model* m, const char* name, int64_t
         // scan of the whole K/V pool (debug, off the hot path): elements the f16_sat clamp of a cache write produced, and the
         // largest magnitude stored (f16 bits; 0x7BFF = 65504 is the clamp)
         if (m->kcache.empty()) return fail(m->ctx, NVLLM_ESTATE, "kv_alloc first");
+        if (!m->k8cache.empty()) { *value = 0; return NVLLM_OK; }  // an 8-bit pool holds no f16 element
         nvllm_ctx* ctx = m->ctx;
         HIPCHK(ctx, hipSetDevice(ctx->device));
         unsigned long long* d = nullptr;
@@ -2843,7 +2905,8 @@ extern "C" int nvllm_op_attention(nvllm_ctx* ctx, const float* q, const float* k
     return nvllm_op_attention_kv(ctx, q, k, v, B, nh, kv, T, hd, scale, 16, 16, out);
 }
 
-// ... with the scratch cache in the given width (16 or 24 bits per K / V element: f16 + one e5m2 residual byte)
+// ... with the scratch cache in the given width (16 or 24 bits per K / V element: f16 + one e5m2 residual byte; or 8 bits
+// for both: e4m3 codes + one f32 scale per token and kv head, through the kernel of attn_kv8.hip)
 extern "C" int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float* k, const float* v, int B, int nh, int kv,
                                      int T, int hd, float scale, int k_bits, int v_bits, float* out) {
     if (!ctx || !q || !k || !v || !out || B < 1 || T < 1) return fail(ctx, NVLLM_EINVAL, "bad attention arguments");
@@ -2863,10 +2926,18 @@ extern "C" int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float
     HIPCHK(ctx, t.get(&qr, (size_t)rows * nh * hd));
     HIPCHK(ctx, t.get(&kr, (size_t)rows * kv * hd));
     HIPCHK(ctx, t.get(&vr, (size_t)rows * kv * hd));
-    HIPCHK(ctx, t.get(&kvl.k, cache_elems));
-    HIPCHK(ctx, t.get(&kvl.v, cache_elems));
-    HIPCHK(ctx, hipMemsetAsync(kvl.k, 0, cache_elems * 2, s));
-    HIPCHK(ctx, hipMemsetAsync(kvl.v, 0, cache_elems * 2, s));
+    if (k_bits == 8) {
+        const size_t scales = (size_t)nblk * kv * kBlockTokens;
+        HIPCHK(ctx, t.get(&kvl.k8, cache_elems)); HIPCHK(ctx, t.get(&kvl.v8, cache_elems));
+        HIPCHK(ctx, t.get(&kvl.ks, scales)); HIPCHK(ctx, t.get(&kvl.vs, scales));
+        HIPCHK(ctx, hipMemsetAsync(kvl.k8, 0, cache_elems, s)); HIPCHK(ctx, hipMemsetAsync(kvl.v8, 0, cache_elems, s));
+        HIPCHK(ctx, hipMemsetAsync(kvl.ks, 0, scales * 4, s)); HIPCHK(ctx, hipMemsetAsync(kvl.vs, 0, scales * 4, s));
+    } else {
+        HIPCHK(ctx, t.get(&kvl.k, cache_elems));
+        HIPCHK(ctx, t.get(&kvl.v, cache_elems));
+        HIPCHK(ctx, hipMemsetAsync(kvl.k, 0, cache_elems * 2, s));
+        HIPCHK(ctx, hipMemsetAsync(kvl.v, 0, cache_elems * 2, s));
+    }
     if (v_bits == 24) {
         HIPCHK(ctx, t.get(&kvl.vlo, cache_elems));
         HIPCHK(ctx, hipMemsetAsync(kvl.vlo, 0, cache_elems, s));
@@ -2899,7 +2970,8 @@ extern "C" int nvllm_op_attention_kv(nvllm_ctx* ctx, const float* q, const float
     AttnArgs a;
     a.q = qr; a.kv = kvl; a.block_tables = dbt; a.max_blocks = bps; a.tile_row0 = dt0; a.tile_nrows = dtn; a.tile_slot = dts;
     a.pos = dpos; a.nh_l = nh; a.gqa = gqa; a.out_f32 = out;
-    HIPCHK(ctx, launch_attn_prefill(a, nt, s));
+    if (k_bits == 8) HIPCHK(ctx, launch_attn_kv8(a, nt, qt, rows, 1, s));
+    else HIPCHK(ctx, launch_attn_prefill(a, nt, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NVLLM_OK;
 }

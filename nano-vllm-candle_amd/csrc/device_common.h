@@ -177,6 +177,36 @@ __device__ __forceinline__ void store_k24(_Float16* k, uint8_t* klo, int t_in_bl
     if (klo) klo[klo_packed_offset(t_in_block, d, hd)] = (uint8_t)kv24_residual(x, h);
 }
 
+// f32 -> e4m3fn code, round to nearest even, saturating (|x| <= 448 after the clamp, so the NaN code is never produced)
+__device__ __forceinline__ uint32_t f32_to_e4m3(float x) {
+    const uint32_t sign = (__builtin_bit_cast(uint32_t, x) >> 24) & 0x80u;
+    const float a = fminf(fabsf(x), 448.f);
+    if (a < 0.015625f) return sign | (uint32_t)__float2int_rn(a * 512.f);  // subnormals: steps of 2^-9; 8 = the smallest normal
+    uint32_t b = __builtin_bit_cast(uint32_t, a);
+    b = (b + 0x7FFFFu + ((b >> 20) & 1u)) >> 20;  // [8 exponent bits][3 mantissa bits]
+    return sign | (b - ((127u - 7u) << 3));
+}
+
+// 8-bit cache (KvLayout::k8 / v8 / ks / vs, head_dim 128): one wave stores one (token, kv head) row; lane holds elements
+// `lane` (x1) and `lane + 64` (x2).  The arithmetic of quant_pack_w8_kernel on a 128-element row: scale = amax / 448 (IEEE
+// f32 division; 1 for an all-zero row), code = nearest-even e4m3 of x / scale, saturating.  Inputs are clamped to the f16
+// cache's +-65504 first, so the scale is always finite.  codes / scales point at the (block, kv head) slab; IS_V picks
+// the PV fragment order (vlo_packed_offset), else the QK^T one (klo_packed_offset).  Every lane of the wave must call.
+template <bool IS_V>
+__device__ __forceinline__ void store_row_kv8(uint8_t* codes, float* scales, int t_in_block, int lane, float x1, float x2) {
+    x1 = fminf(fmaxf(x1, -65504.f), 65504.f);
+    x2 = fminf(fmaxf(x2, -65504.f), 65504.f);
+    float amax = fmaxf(fabsf(x1), fabsf(x2));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    const float scale = amax > 0.f ? amax / 448.f : 1.f;
+    const size_t o1 = IS_V ? vlo_packed_offset(t_in_block, lane, 128) : klo_packed_offset(t_in_block, lane, 128);
+    const size_t o2 = IS_V ? vlo_packed_offset(t_in_block, lane + 64, 128) : klo_packed_offset(t_in_block, lane + 64, 128);
+    codes[o1] = (uint8_t)f32_to_e4m3(x1 / scale);
+    codes[o2] = (uint8_t)f32_to_e4m3(x2 / scale);
+    if (lane == 0) scales[t_in_block] = scale;
+}
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 

@@ -224,6 +224,12 @@ struct KvLayout {
     f16_bits* v = nullptr;  // [num_blocks][kv_l][8 tiles][hd/16][64 lanes][8] f16 (PV A-fragment packed)
     uint8_t* vlo = nullptr; // optional 24-bit V: e5m2 rounding residual of every V element, same element order (1 byte each)
     uint8_t* klo = nullptr; // optional 24-bit K (only together with vlo): the same for K (device_common.h: klo_packed_offset)
+    // 8-bit cache (attn_kv8.hip; k8 set => k, v, vlo, klo unused, hd = 128): every (token, kv head) row of K and of V is 128 OCP
+    // e4m3fn codes and one f32 scale = row amax / 448 (1 for an all-zero row); value = scale * e4m3(code)
+    uint8_t* k8 = nullptr;  // K codes, one byte per element at klo_packed_offset: two QK^T A-fragments per 16-byte lane slot
+    uint8_t* v8 = nullptr;  // V codes at vlo_packed_offset: two PV A-fragments per 16-byte lane slot
+    float* ks = nullptr;    // K scales [num_blocks][kv_l][256 tokens]; zero until a token is written
+    float* vs = nullptr;    // V scales, likewise
     int kv_l = 0, hd = 0;
 };
 struct QkvArgs {
@@ -338,6 +344,15 @@ inline int attn_tokens_per_tile(int gqa, int qt) { return (16 / gqa) * qt; }
 // 4b..4b+3 belong to one sequence (tile_slot[4b]), a sequence's last group is padded with empty tiles (tile_nrows = 0)
 constexpr int kPrefillTileGroup = 4;
 hipError_t launch_attn_prefill(const AttnArgs& a, int n_tiles, hipStream_t s);
+// merge pass of the split-KV forms: sums the partials (part_o, part_ml) of every row that has more than one part
+hipError_t launch_attn_combine(const AttnArgs& a, int rows, hipStream_t s);
+
+// ---- paged attention on the 8-bit cache (attn_kv8.hip; KvLayout::k8 / v8 / ks / vs, head_dim 128) -----------------------
+// Arguments as launch_attn_paged without the fused prologue (q from the row kernel, qkv == nullptr); an empty q-tile
+// (tile_nrows = 0, the padding of the prefill tile groups) is skipped.  A wave step is one 64-token tile (16 KiB of codes),
+// so a split context needs an even part_tiles (kAttnKv8TileSteps 32-token tiles per step).
+constexpr int kAttnKv8TileSteps = 2;
+hipError_t launch_attn_kv8(const AttnArgs& a, int n_tiles, int qt, int rows, int n_parts_max, hipStream_t s);
 
 // ---- work-balanced decode attention (opt-in schedule; head_dim 128, fused prologue, one row per sequence) ----------
 // The 32-token K/V tiles of every sequence, longest context first (AttnArgs::tile_order), laid end to end and cut into

@@ -1794,6 +1794,11 @@ __global__ void __launch_bounds__(256) qk_norm_rope_kvwrite_kernel(QkvArgs a) {
                 q[lane] = y1 * a.q_scale;
                 q[lane + half] = y2 * a.q_scale;
             }
+        } else if (a.kv.k8) {  // 8-bit cache (hd 128: every lane holds two elements of the row)
+            const int kh = hh - a.nh_l;
+            const int blk = a.block_tables[(size_t)a.slot[row] * a.max_blocks + (pos >> 8)];
+            const size_t slab = (size_t)blk * kv_l + kh;
+            store_row_kv8<false>(a.kv.k8 + slab * kBlockTokens * hd, a.kv.ks + slab * kBlockTokens, pos & 255, lane, y1, y2);
         } else if (act) {
             const int kh = hh - a.nh_l;
             const int blk = a.block_tables[(size_t)a.slot[row] * a.max_blocks + (pos >> 8)];
@@ -1803,6 +1808,11 @@ __global__ void __launch_bounds__(256) qk_norm_rope_kvwrite_kernel(QkvArgs a) {
             store_k24(k, klo, pos & 255, lane, hd, y1);
             store_k24(k, klo, pos & 255, lane + half, hd, y2);
         }
+    } else if (a.kv.k8) {
+        const int kh = hh - a.nh_l - kv_l;
+        const int blk = a.block_tables[(size_t)a.slot[row] * a.max_blocks + (pos >> 8)];
+        const size_t slab = (size_t)blk * kv_l + kh;
+        store_row_kv8<true>(a.kv.v8 + slab * kBlockTokens * hd, a.kv.vs + slab * kBlockTokens, pos & 255, lane, x1, x2);
     } else if (act) {  // v head: plain copy into the packed layout
         const int kh = hh - a.nh_l - kv_l;
         const int blk = a.block_tables[(size_t)a.slot[row] * a.max_blocks + (pos >> 8)];
@@ -1816,6 +1826,7 @@ __global__ void __launch_bounds__(256) qk_norm_rope_kvwrite_kernel(QkvArgs a) {
 
 hipError_t launch_qk_norm_rope_kvwrite(const QkvArgs& a, int rows, hipStream_t s) {
     if (a.kv.hd > 128 || a.kv.hd % 32 != 0) return hipErrorInvalidValue;
+    if (a.kv.k8 && (a.kv.hd != 128 || !a.kv.v8 || !a.kv.ks || !a.kv.vs)) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
     const int heads = a.nh_l + 2 * a.kv.kv_l;
     dim3 grid(rows, (heads + 3) / 4);
@@ -1831,6 +1842,15 @@ __global__ void __launch_bounds__(256) kv_write_plain_kernel(const float* __rest
     const int n = kv.kv_l * kv.hd;
     const int p = pos[row];
     const int blk = bt[(size_t)slot[row] * max_blocks + (p >> 8)];
+    if (kv.k8) {  // 8-bit cache (hd 128): one wave per kv head, a lane holds elements lane and lane + 64 of the row
+        const int lane = threadIdx.x & 63;
+        for (int kh = threadIdx.x >> 6; kh < kv.kv_l; kh += 4) {
+            const size_t slab = (size_t)blk * kv.kv_l + kh, src = (size_t)row * n + (size_t)kh * 128 + lane;
+            store_row_kv8<false>(kv.k8 + slab * kBlockTokens * 128, kv.ks + slab * kBlockTokens, p & 255, lane, k[src], k[src + 64]);
+            store_row_kv8<true>(kv.v8 + slab * kBlockTokens * 128, kv.vs + slab * kBlockTokens, p & 255, lane, v[src], v[src + 64]);
+        }
+        return;
+    }
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int kh = i / kv.hd, d = i - kh * kv.hd;
         const size_t vo = (size_t)(blk * kv.kv_l + kh) * kBlockTokens * kv.hd;
@@ -1841,6 +1861,7 @@ __global__ void __launch_bounds__(256) kv_write_plain_kernel(const float* __rest
 hipError_t launch_kv_write_plain(const float* k, const float* v, int rows, const int* pos, const int* slot,
                                  const int* block_tables, int max_blocks, KvLayout kv, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
+    if (kv.k8 && (kv.hd != 128 || !kv.v8 || !kv.ks || !kv.vs)) return hipErrorInvalidValue;
     kv_write_plain_kernel<<<rows, 256, 0, s>>>(k, v, pos, slot, block_tables, max_blocks, kv);
     return hipGetLastError();
 }
@@ -2868,6 +2889,14 @@ hipError_t launch_attn_prefill(const AttnArgs& a, int n_tiles, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_attn_combine(const AttnArgs& a, int rows, hipStream_t s) {
+    const int items = rows * a.nh_l;
+    if (items <= 0) return hipSuccess;
+    if (a.kv.hd == 128) attn_combine_kernel<128><<<(items + 3) / 4, 256, 0, s>>>(a, rows);
+    else attn_combine_kernel<64><<<(items + 3) / 4, 256, 0, s>>>(a, rows);
+    return hipGetLastError();
+}
+
 // rows: number of q rows (needed by the combine pass); n_parts_max: ceil(max context tiles / part_tiles)
 hipError_t launch_attn_paged(const AttnArgs& a, int n_tiles, int qt, int rows, int n_parts_max, hipStream_t s) {
     if (n_tiles <= 0) return hipSuccess;
@@ -2885,10 +2914,7 @@ hipError_t launch_attn_paged(const AttnArgs& a, int n_tiles, int qt, int rows, i
     else if (a.kv.hd == 64 && qt == 1) e = fused ? attn_launch_t<64, 1, 4, true>(b, n_tiles, gz, s) : attn_launch_t<64, 1, 4, false>(b, n_tiles, gz, s);
     else if (a.kv.hd == 64 && qt == 2) e = attn_launch_t<64, 2, 4, false>(b, n_tiles, gz, s);
     if (e != hipSuccess || !split) return e;
-    const int items = rows * a.nh_l;
-    if (a.kv.hd == 128) attn_combine_kernel<128><<<(items + 3) / 4, 256, 0, s>>>(b, rows);
-    else attn_combine_kernel<64><<<(items + 3) / 4, 256, 0, s>>>(b, rows);
-    return hipGetLastError();
+    return launch_attn_combine(b, rows, s);
 }
 
 // ---------------------------------------------------------------------------------------------------

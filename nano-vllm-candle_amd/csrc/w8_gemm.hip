@@ -188,16 +188,6 @@ __device__ __forceinline__ int w8_dest_row(int row0, int rl, int ileave) {
     return ileave < 0 ? row0 + rl : (((rl >> 4) * 2 + ileave) << 4) + (rl & 15);
 }
 
-// f32 -> e4m3fn code, round to nearest even, saturating (|x| <= 448 after the clamp, so the NaN code is never produced)
-__device__ __forceinline__ uint32_t f32_to_e4m3(float x) {
-    const uint32_t sign = (__builtin_bit_cast(uint32_t, x) >> 24) & 0x80u;
-    const float a = fminf(fabsf(x), 448.f);
-    if (a < 0.015625f) return sign | (uint32_t)__float2int_rn(a * 512.f);  // subnormals: steps of 2^-9; 8 = the smallest normal
-    uint32_t b = __builtin_bit_cast(uint32_t, a);
-    b = (b + 0x7FFFFu + ((b >> 20) & 1u)) >> 20;  // [8 exponent bits][3 mantissa bits]
-    return sign | (b - ((127u - 7u) << 3));
-}
-
 __global__ void __launch_bounds__(256) quant_pack_w8_kernel(uint4* __restrict__ codes, float* __restrict__ scales, int KB, int dst_row0,
                                                             int ileave, int rows, int row_phase, const uint16_t* __restrict__ src,
                                                             int64_t ld, const uint4* __restrict__ src_packed) {

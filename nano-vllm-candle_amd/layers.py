@@ -256,7 +256,7 @@ class Attention:
     """The attention `layers::Attention` names (src/layers/attention.rs:4-16 is a dead sdpa wrapper): causal GQA
     attention with the live path's math (src/models/qwen3.rs:236-277).  forward(q [B,nh,T,hd], k, v [B,kv,T,hd])
     -> ctx [B*T, nh*hd].  softcapping must be 0 (the live path has none).  kv_bits = (k_bits, v_bits): width of the
-    scratch K/V cache the op runs on, 16 or 24 bits each (Qwen3ForCausalLM.set_kv_cache_bits)."""
+    scratch K/V cache the op runs on, 16 or 24 bits each or (8, 8) (Qwen3ForCausalLM.set_kv_cache_bits)."""
 
     def __init__(self, num_heads, head_dim, scale, softcapping=0.0, ctx=None, kv_bits=(16, 16)):
         if softcapping not in (0, 0.0, 1.0):

@@ -227,7 +227,9 @@ class Qwen3ForCausalLM:
     # ---- KV pool ----
     def set_kv_cache_bits(self, k_bits, v_bits):
         """Width of the K / V cache elements for the NEXT kv_alloc: 16 (f16) or 24 (f16 + an e5m2 residual byte) each;
-        24-bit K only together with 24-bit V, and head_dim 128.  Anything else raises NvllmError (EINVAL)."""
+        24-bit K only together with 24-bit V, and head_dim 128.  (8, 8): e4m3 codes plus one f32 scale per token and kv
+        head -- 132 bytes per row instead of 256, read by an attention kernel of its own; head_dim 128, K and V together.
+        Anything else raises NvllmError (EINVAL)."""
         _lib.check(_lib.lib().nvllm_model_set_kv_cache_bits(self.h, int(k_bits), int(v_bits)), self.ctx.h)
 
     ATTENTION_SCHEDULES = {"per_sequence": 0, "balanced": 1, "shared_prefix": 2}
